@@ -4,11 +4,15 @@ voxel_down_sample + estimate_normals (KNN30), plus ICP iterations/s.
 
 N = 1 (default): C2 — one synthetic uniform-random 10M-point float32 cloud
 resident in HBM; one step = voxel_down_sample(vs=(4/N)^(1/3)) ->
-estimate_normals(KNN 30) on the M representatives.  Secondary figures on the
-same GPU: C3 (RANSAC 1000 hypotheses + point-to-plane ICP 30 iterations at
-10M), C4's size on one GPU (50M) and C5 (200M full pipeline incl. ICP), and
-the CPU baselines (the oracle, an Open3D-equivalent C++ restatement) of the
-voxel+normals step, RANSAC and ICP on the same inputs.
+estimate_normals(KNN 30) on the M representatives.  A plain run sets up,
+warms up, times --steps steps, writes the last step's outputs if
+--dump-outputs DIR is given and prints the result line.  With --full, after
+that: the per-kernel breakdown pass, the other call structure, and the
+secondary figures on the same GPU: C3 (RANSAC 1000 hypotheses +
+point-to-plane ICP 30 iterations at 10M), C4's size on one GPU (50M), C5
+(200M full pipeline incl. ICP), the float64 scan, and the CPU baselines (the
+oracle, an Open3D-equivalent C++ restatement) of the voxel+normals step,
+RANSAC and ICP on the same inputs.
 
 N > 1 (one process per GPU, RCCL): C2 per GPU, weak scaling — ONE
 uniform-random cloud of N x 10M points over [0,N) x [0,1)^2 (the C2 density,
@@ -65,6 +69,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=25,
                     help="untimed steps first (the clocks settle over ~20 steps: profiles/r02_call_structure.txt)")
+    ap.add_argument("--full", action="store_true",
+                    help="one GPU: after the headline also the per-kernel breakdown pass, the other call structure, "
+                         "the CPU baselines and the secondary legs (C3, C4, C5, float64); without it a run does "
+                         "only what the headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one GPU: write what the last timed step returned (rep_idx, rep_xyz, normals; a fixed "
+                         "seeded sample of rows when they exceed the size budget) as DIR/<name>.npy")
     ap.add_argument("--n", type=int, default=10_000_000, help="points per GPU (C2: 10M)")
     ap.add_argument("--knn", type=int, default=30)
     ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
@@ -94,7 +105,10 @@ def parse():
                          "prints a placeholder line (checks the --gpus N launcher on a CPU host)")
     ap.add_argument("--child-timeout", type=int, default=900,
                     help="seconds one rank count of the --gpus N sweep may take before its processes are killed")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--dump-outputs writes the one-GPU step's outputs: use it with --gpus 1")
+    return args
 
 
 def setup_dist(force=False):
@@ -606,6 +620,31 @@ def c5_sharded(dev, args, world, rank):
     return {"c5_sharded": res}
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # all files of one --dump-outputs together
+
+
+def dump_outputs(dirname, out):
+    """--dump-outputs: the arrays the timed call handed back in its last
+    step, one row per voxel representative, as DIR/<name>.npy: rep_idx
+    (float64, the int32 indices exactly), rep_xyz and normals (float32), and
+    rows (float64), the output rows the files hold: all M of them, or, when
+    that would exceed DUMP_BUDGET_BYTES, a sorted sample drawn with a fixed
+    seed (a function of M alone, so two builds that agree on M dump the same
+    rows)."""
+    os.makedirs(dirname, exist_ok=True)
+    m = int(out["rep_idx"].shape[0])
+    row_bytes = 8 + 8 + 12 + 12  # rows, rep_idx, rep_xyz, normals
+    if m * row_bytes > DUMP_BUDGET_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(m, size=DUMP_BUDGET_BYTES // row_bytes, replace=False))
+    else:
+        rows = np.arange(m)
+    sel = torch.from_numpy(rows).to(out["rep_idx"].device)
+    np.save(os.path.join(dirname, "rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(dirname, "rep_idx.npy"), out["rep_idx"][sel].cpu().numpy().astype(np.float64))
+    for name in ("rep_xyz", "normals"):
+        np.save(os.path.join(dirname, name + ".npy"), out[name][sel].cpu().numpy().astype(np.float32))
+
+
 def kernel_table():
     kernels = {}
     for name in ("voxel_assign", "voxel_compact", "grid_count", "grid_sort", "normals_stile", "normals_tile",
@@ -686,18 +725,23 @@ def main():
     pts = synthetic.uniform_cube(N, seed=0, device=dev)
     torch.cuda.synchronize(dev)
     keep = not args.sorted_grid
+    last = {}  # --dump-outputs: what the latest step returned
 
     def step_two_call():
         # PointCloud.voxel_down_sample(vs).estimate_normals(): the voxel table
         # of the first call is the search grid of the second
         out = ops.voxel_down_sample(pts, vs, keep_grid=keep)
         nrm = ops.estimate_normals(out["rep_xyz"], knn=args.knn, voxel_grid=out.get("voxel_grid"))
+        if args.dump_outputs:
+            last.update(rep_idx=out["rep_idx"], rep_xyz=out["rep_xyz"], normals=nrm)
         return out["rep_idx"].numel(), nrm
 
     def step_fused():
         # the same pipeline as one library call: the normals are queued behind
         # the voxel kernels before the representative count is read back
         out = ops.voxel_down_sample_normals(pts, vs, knn=args.knn)
+        if args.dump_outputs:
+            last.update(rep_idx=out["rep_idx"], rep_xyz=out["rep_xyz"], normals=out["normals"])
         return out["rep_idx"].numel(), out["normals"]
 
     step = step_two_call if (args.two_call or not keep) else step_fused
@@ -725,19 +769,25 @@ def main():
     ev_ms = ev0.elapsed_time(ev1)
     dom = kernel_table()
     _native.kernel_timing_filter(None)
-    _native.reset_kernel_timing()
-    _native.set_kernel_timing(True)
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize(dev)
-    _native.set_kernel_timing(False)
-    kernels = kernel_table()  # breakdown (all timers on; not the timed region)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
+        last.clear()
+        args.dump_outputs = None  # the later passes keep nothing
+    kernels = {}
+    if args.full:
+        _native.reset_kernel_timing()
+        _native.set_kernel_timing(True)
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize(dev)
+        _native.set_kernel_timing(False)
+        kernels = kernel_table()  # breakdown (all timers on; not the timed region)
     if dom:
         kernels.update(dom)   # the dominant kernel as timed inside the timed region
     value = float(N) * args.steps / elapsed / 1e6
     other = step_two_call if step is step_fused else (step_fused if keep else None)
     other_ms = None
-    if other is not None:  # the other call structure, same pipeline, for the record
+    if args.full and other is not None:  # the other call structure, same pipeline, for the record
         other()
         torch.cuda.synchronize(dev)
         ta = time.perf_counter()
@@ -762,7 +812,7 @@ def main():
                   "pipeline_algorithmic_GBs": round((12.0 * N + 28.0 * M) * args.steps / elapsed / 1e9, 2),
                   "storage_dtype": "f32", "arith": "float64 voxel keys / distances / covariance"},
     }
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         line["cpu_baseline"] = cpu_baseline(args.cpu_n, pts)
         if line["cpu_baseline"]["value"] > 0:
             line["extra"]["gpu_over_cpu"] = round(value / line["cpu_baseline"]["value"], 1)
@@ -773,7 +823,7 @@ def main():
             line["extra"].update(c4_single_gpu(dev, args))
         except RuntimeError as e:
             line["extra"]["c4_error"] = str(e)
-    elif not args.no_secondary:
+    elif args.full and not args.no_secondary:
         for name, fn in (("secondary", lambda: secondary(dev, args)),
                          ("c4", lambda: c4_single_gpu(dev, args) if args.c4_n > 0 else {}),
                          ("c5", lambda: c5_pipeline(dev, args) if args.c5_n > 0 else {}),
@@ -992,7 +1042,8 @@ def launch(args):
     base = _strip_gpus(sys.argv[1:])
     runs, errors = {}, []
     for n in _rank_counts(N):
-        argv = list(base) + ["--no-cpu"] + ([] if n == N else ["--scaling-child"])
+        # --full: the 1-rank point keeps its breakdown pass (more ranks ignore it)
+        argv = list(base) + ["--no-cpu", "--full"] + ([] if n == N else ["--scaling-child"])
         log(f"bench launcher: {n} rank(s)")
         line, err = _run_ranks(n, argv, args.child_timeout)
         if err:
