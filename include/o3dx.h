@@ -719,6 +719,38 @@ int o3dx_registration_icp_point_to_plane_f64(
     int32_t* corr_out_dev, int64_t* ncorr_host, void* target_ws, size_t target_ws_bytes, void* ws,
     size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------ clustering
+ * DBSCAN (reference PointCloud.py:921-927: sklearn.cluster.DBSCAN(eps,
+ * min_samples).fit(get_points()).labels_), additive to ABI 7.  The labels are
+ * sklearn's, a deterministic function of the input:
+ *   1. neighbourhood: j is a neighbour of i when d^2(i,j) <= eps*eps —
+ *      inclusive, unlike the strict < of the Open3D radius searches above —
+ *      and i is its own neighbour; d^2 = ((dx dx) + dy dy) + dz dz in float64
+ *      on the float64 coordinates (float32 points upcast exactly);
+ *   2. core: |N(i)| >= min_samples;
+ *   3. clusters: the connected components of the core points under the
+ *      neighbour relation, numbered 0, 1, ... in ascending order of each
+ *      component's smallest core index;
+ *   4. border: a non-core point with at least one core neighbour takes the
+ *      smallest label among its core neighbours;
+ *   5. noise: every other point is -1.
+ * labels_dev (n int32) and core_dev (n bytes, 1 = core; nullable) are in the
+ * original point order; *n_clusters_host receives the cluster count.  The
+ * coordinates must be finite.  The result does not depend on launch order (no
+ * float atomics).  o3dx_dbscan_f64 decides every pair from the caller's
+ * float64 coordinates (the float64 boundary above).
+ * Errors, checked before any device call: EINVAL for n <= 0, n >= 2^31,
+ * eps <= 0 or not finite, min_samples < 1, a null xyz / labels /
+ * n_clusters_host; ENOMEM for a workspace below o3dx_dbscan*_workspace_bytes(n)
+ * (0 for an n outside the range).  EIO if the union-find's iteration bound is
+ * exceeded (never, unless memory is corrupted).  Synchronises the stream. */
+size_t o3dx_dbscan_workspace_bytes(int64_t n);
+int o3dx_dbscan(const float* xyz_dev, int64_t n, double eps, int min_samples, int32_t* labels_dev,
+                uint8_t* core_dev, int64_t* n_clusters_host, void* ws, size_t ws_bytes, void* stream);
+size_t o3dx_dbscan_f64_workspace_bytes(int64_t n);
+int o3dx_dbscan_f64(const double* xyz_dev, int64_t n, double eps, int min_samples, int32_t* labels_dev,
+                    uint8_t* core_dev, int64_t* n_clusters_host, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

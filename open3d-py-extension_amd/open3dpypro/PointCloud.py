@@ -15,9 +15,10 @@ the reference.
 
 The hot-path methods call libo3dx.so (ops.py); there is no CPU fallback —
 without an MI355X they raise RuntimeError.  Host-only helpers (selections by
-numpy predicate, splitting, I/O) run anywhere.  Out of scope (SURVEY.md §2
-rows 2 and 5) and not mirrored: DBSCAN, to_2D_Img, the colour-cosine
-selections.
+numpy predicate, splitting, I/O) run anywhere.  DBSCAN (the reference's
+sklearn call) runs on the GPU and returns sklearn's labels (ops.dbscan).  Out
+of scope and not mirrored: to_2D_Img, the
+colour-cosine selections.
 """
 from __future__ import annotations
 
@@ -897,6 +898,37 @@ class PointCloud(PointCloudUtility):
         pcds.append(rest)
         aabbs.append(rest.get_aabb())
         return planes, pcds, aabbs
+
+    def DBSCAN(self, eps: float = 0.05, min_samples: int = 3):
+        """sklearn.cluster.DBSCAN(eps, min_samples).fit(get_points()) on the GPU
+        (reference PointCloud.py:921-927) -> ([cloud per cluster], labels).
+        labels: sklearn's labels_ (int64 numpy; clusters numbered by ascending
+        smallest core index, noise -1); cluster i is _select_by_idx of the
+        ascending indices with label i, every attribute carried.  ValueError,
+        as sklearn raises, for eps <= 0, min_samples < 1, an empty cloud or
+        non-finite coordinates.  sklearn's other arguments (metric,
+        sample_weight, n_jobs) are not offered."""
+        eps = float(eps)
+        if not (eps > 0.0) or not np.isfinite(eps):
+            raise ValueError(f"eps must be a finite float > 0, got {eps}")
+        if int(min_samples) != min_samples or int(min_samples) < 1:
+            raise ValueError(f"min_samples must be an int >= 1, got {min_samples}")
+        if not self.has_points():
+            raise ValueError("Found array with 0 sample(s) (shape=(0, 3)) while a minimum of 1 is required by DBSCAN.")
+        if self._pts_host is not None:
+            finite = bool(np.isfinite(self._pts_host).all())
+        else:
+            src = self._pts64 if self._pts64 is not None else self._pts
+            finite = bool(torch.isfinite(src).all().item())
+        if not finite:
+            raise ValueError("Input contains NaN or infinity.")
+        lab, k = ops.dbscan(self._hot_points(), eps, int(min_samples))
+        # one stable sort groups the indices by label, ascending inside each
+        order = torch.sort(lab, stable=True).indices
+        counts = torch.bincount((lab + 1).long(), minlength=k + 1).cpu().numpy()
+        ends = np.cumsum(counts)  # label -1 first
+        pcds = [self._select_by_idx(order[ends[i]:ends[i + 1]]) for i in range(k)]
+        return pcds, lab.cpu().numpy().astype(np.int64)
 
     def registration_icp(self, target: "PointCloudBase", max_correspondence_distance: float, init=None,
                          max_iteration: int = 30, relative_fitness: float = 1e-6, relative_rmse: float = 1e-6):

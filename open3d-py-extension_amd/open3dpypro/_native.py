@@ -137,6 +137,11 @@ _SIGS = {
                                    _P]),
     "o3dx_slab_halo_merge": (_I32, [_P, _P, _P, _I64, _P, _I64, _I64, _P, _I64, _P, _P, _P]),
     "o3dx_slab_verdict": (_I32, [_P, _P, _P, _I64, _P, _P, _D, _D, _I32, _I32, _D, _P, _P, _P, _P, _P]),
+    # clustering (additive to ABI 7)
+    "o3dx_dbscan_workspace_bytes": (_SZ, [_I64]),
+    "o3dx_dbscan": (_I32, [_P, _I64, _D, _I32, _P, _P, _P, _P, _SZ, _P]),
+    "o3dx_dbscan_f64_workspace_bytes": (_SZ, [_I64]),
+    "o3dx_dbscan_f64": (_I32, [_P, _I64, _D, _I32, _P, _P, _P, _P, _SZ, _P]),
 }
 
 _lib = None

@@ -371,6 +371,41 @@ def search_one(xyz: torch.Tensor, query, mode: int = N.SEARCH_KNN, knn: int = 30
     return k, idx[:k], d2[:k]
 
 
+def dbscan(xyz: torch.Tensor, eps: float, min_samples: int, return_core: bool = False):
+    """sklearn.cluster.DBSCAN(eps, min_samples).fit(xyz) on the device
+    (o3dx_dbscan; include/o3dx.h states the rule): (labels (n,) int32 device
+    tensor, n_clusters[, core (n,) bool device tensor]).  Labels are sklearn's:
+    clusters numbered by ascending smallest core index, noise -1.  float64
+    points: o3dx_dbscan_f64 (every pair decided on the float64 coordinates).
+    ValueError, as sklearn, for eps <= 0, min_samples < 1 or no points."""
+    eps = float(eps)
+    if not (eps > 0.0) or not np.isfinite(eps):
+        raise ValueError(f"eps must be a finite float > 0, got {eps}")
+    if int(min_samples) != min_samples or int(min_samples) < 1:
+        raise ValueError(f"min_samples must be an int >= 1, got {min_samples}")
+    if isinstance(xyz, torch.Tensor) and xyz.ndim == 2 and xyz.shape[0] == 0:
+        raise ValueError("dbscan: found a cloud with 0 points (a minimum of 1 is required)")
+    f64 = _is64(xyz)
+    x = _xyz64(xyz) if f64 else _xyz(xyz)
+    L = N.load()
+    n = x.shape[0]
+    dev = x.device
+    labels = torch.empty(n, dtype=torch.int32, device=dev)
+    core = torch.empty(n, dtype=torch.uint8, device=dev) if return_core else None
+    cnt = np.zeros(1, np.int64)
+    if f64:
+        ws = N.workspace(L.o3dx_dbscan_f64_workspace_bytes(n), dev)
+        fn = L.o3dx_dbscan_f64
+    else:
+        ws = N.workspace(L.o3dx_dbscan_workspace_bytes(n), dev)
+        fn = L.o3dx_dbscan
+    N.check(fn(N.ptr(x), n, eps, int(min_samples), N.ptr(labels), N.ptr(core), _np_ptr(cnt), N.ptr(ws), ws.numel(),
+               N.stream_ptr(dev)), "dbscan")
+    if return_core:
+        return labels, int(cnt[0]), core.bool()
+    return labels, int(cnt[0])
+
+
 def ransac_samples(n: int, ransac_n: int, num_iterations: int, seed: int) -> np.ndarray:
     """Open3D RandomSampler over mt19937(seed): (iters, ransac_n) int32."""
     out = np.empty((max(num_iterations, 1), ransac_n), np.int32)
