@@ -59,7 +59,9 @@ extern "C" {
  *   [27]     sum r^2         (point-to-plane residuals)
  *   [28]     correspondence count
  *   [29]     sum d^2         (squared correspondence distances, for inlier_rmse)
- *   [30..31] reserved (0) */
+ *   [30..31] reserved (0)
+ * (point-to-point estimation: its own layout in the same vector, "Point-to-point
+ * ICP" below; [28] and [29] keep their meaning) */
 #define O3DX_ICP_NSUMS 32
 /* length of the ICP target descriptor (doubles) */
 #define O3DX_ICP_DESC_LEN 24
@@ -560,6 +562,104 @@ int o3dx_registration_icp_point_to_plane(
     double* T_out_host, double* fitness_host, double* inlier_rmse_host,
     int32_t* corr_out_dev, int64_t* ncorr_host, void* target_ws,
     size_t target_ws_bytes, void* ws, size_t ws_bytes, void* stream);
+
+/* Point-to-point ICP (additive to ABI 7): Open3D's registration_icp with
+ * TransformationEstimationPointToPoint(with_scaling), its default estimation.
+ * The loop, the correspondences and the convergence test are those above;
+ * the update is Eigen::umeyama(P, Q, with_scaling) of the matched, already
+ * transformed source points P and their target points Q: [cR | t], R = U S
+ * V^T of the covariance (1/n) sum (q - qm)(p - pm)^T, S = diag(1, 1, +-1),
+ * c = 1 or (s . diag S) / var(p), t = qm - c R pm.  It needs no target
+ * normals.  `estimation` is one of the constants below (anything else:
+ * O3DX_EINVAL, before any device call).
+ *
+ * Point-to-point sums (sums_host[O3DX_ICP_NSUMS]): the moments are taken
+ * about a fixed anchor a, the target grid's origin (a float64 target's frame
+ * origin), p' = p - a and q' = q - a in float64, so that a cloud far from the
+ * coordinate origin loses nothing to cancellation:
+ *   [0..8]   sum q'_a p'_b, row-major (3x3)
+ *   [9..11]  sum p'
+ *   [12..14] sum q'
+ *   [15]     sum |p'|^2
+ *   [16..18] the anchor a itself (set by the library; its fx rows are 0)
+ *   [28]     correspondence count, [29] sum d^2 (as above); all others 0
+ * The fx quanta follow from |q'| <= D (the target grid box's diagonal plus
+ * its slack) and |p'| <= D + max_correspondence_distance, so they depend on
+ * neither T nor the clouds' offset.  o3dx_icp_accumulate_est returns this
+ * estimation's fx rows with the low digits' carry moved up (lo < 2^32), so
+ * the rows themselves, not only their values, are the same for any order of
+ * the source.
+ *
+ * o3dx_icp_target_build_points[_f64]: a target without normals (workspace as
+ *   o3dx_icp_target_build[_f64]).  The point-to-plane entries refuse its
+ *   descriptor (O3DX_EINVAL); point-to-point takes either kind of target.
+ * o3dx_icp_accumulate_est, o3dx_icp_register_est[_f64],
+ *   o3dx_registration_icp_est[_f64]: the entries above with the estimation
+ *   (and with_scaling); tgt_normals_dev may be NULL for point-to-point.
+ * o3dx_icp_solve_point_to_point / o3dx_icp_update_est: host only, the solve
+ *   the device loop runs (the same bits); 1 if solved, 0 for the identity
+ *   update (no correspondences, or a non-finite result such as with_scaling
+ *   on a source of zero spread). */
+#define O3DX_ICP_POINT_TO_PLANE 0
+#define O3DX_ICP_POINT_TO_POINT 1
+int o3dx_icp_target_build_points(const float* tgt_dev, int64_t nt,
+                                 double max_correspondence_distance,
+                                 void* target_ws, size_t target_ws_bytes,
+                                 double* desc_host, void* stream);
+int o3dx_icp_accumulate_est(const float* src_dev, int64_t ns, int src_sorted4,
+                            const void* target_ws, const double* desc_host,
+                            const double* T_host,
+                            double max_correspondence_distance,
+                            const double* src_absmax_host, double* sums_host,
+                            int64_t* fx_out_host, int32_t* corr_out_dev,
+                            int64_t* ncorr_host, int estimation, void* ws,
+                            size_t ws_bytes, void* stream);
+int o3dx_icp_register_est(const float* src_dev, int64_t ns, int src_sorted4,
+                          const void* target_ws, const double* desc_host,
+                          const double* init_host, int max_iteration,
+                          double relative_fitness, double relative_rmse,
+                          double max_correspondence_distance,
+                          const double* src_absmax_host, double* T_out_host,
+                          double* fitness_host, double* inlier_rmse_host,
+                          int32_t* corr_out_dev, int64_t* ncorr_host,
+                          int estimation, int with_scaling, void* ws,
+                          size_t ws_bytes, void* stream);
+int o3dx_registration_icp_est(
+    const float* src_dev, int64_t ns, const float* tgt_dev,
+    const float* tgt_normals_dev, int64_t nt,
+    double max_correspondence_distance, const double* init_host,
+    int max_iteration, double relative_fitness, double relative_rmse,
+    double* T_out_host, double* fitness_host, double* inlier_rmse_host,
+    int32_t* corr_out_dev, int64_t* ncorr_host, int estimation,
+    int with_scaling, void* target_ws, size_t target_ws_bytes, void* ws,
+    size_t ws_bytes, void* stream);
+int o3dx_icp_solve_point_to_point(const double* sums_host, int with_scaling,
+                                  double* update_host);
+int o3dx_icp_update_est(const double* sums_host, int estimation,
+                        int with_scaling, double* T_host);
+int o3dx_icp_target_build_points_f64(const double* tgt_dev, int64_t nt,
+                                     double max_correspondence_distance,
+                                     void* target_ws, size_t target_ws_bytes,
+                                     double* desc_host, void* stream);
+int o3dx_icp_register_est_f64(const double* src_dev, int64_t ns, int src_sorted4,
+                              const void* target_ws, const double* desc_host,
+                              const double* init_host, int max_iteration,
+                              double relative_fitness, double relative_rmse,
+                              double max_correspondence_distance,
+                              const double* src_absmax_host, double* T_out_host,
+                              double* fitness_host, double* inlier_rmse_host,
+                              int32_t* corr_out_dev, int64_t* ncorr_host,
+                              int estimation, int with_scaling, void* ws,
+                              size_t ws_bytes, void* stream);
+int o3dx_registration_icp_est_f64(
+    const double* src_dev, int64_t ns, const double* tgt_dev,
+    const float* tgt_normals_dev, int64_t nt,
+    double max_correspondence_distance, const double* init_host,
+    int max_iteration, double relative_fitness, double relative_rmse,
+    double* T_out_host, double* fitness_host, double* inlier_rmse_host,
+    int32_t* corr_out_dev, int64_t* ncorr_host, int estimation,
+    int with_scaling, void* target_ws, size_t target_ws_bytes, void* ws,
+    size_t ws_bytes, void* stream);
 
 /* Sharded ICP device loop (ABI 7; distributed.registration_icp_sharded, the
  * north star's "6x6 JTJ RCCL all-reduce", SURVEY 8(e) ICP row).  Each rank

@@ -19,6 +19,13 @@
 // (the build has -ffp-contract=off; division and sqrt are correctly rounded on
 // both sides; sin / cos are the library's own), so the host loop of a sharded
 // source (distributed.py, o3dx_icp_update) reaches the same T to the bit.
+//
+// Point-to-point (TransformationEstimationPointToPoint, Open3D's default
+// estimation; Eigen::umeyama restated, with_scaling optional) runs on the same
+// loop: the estimation is a template parameter of the step and of the finish.
+// Its step reads no normals and forms 18 moments about a fixed anchor (the
+// target grid's origin); its solve is a 3x3 Jacobi SVD, again one __host__
+// __device__ function (solve_update_p2p).
 #include <cfloat>
 #include <vector>
 
@@ -202,6 +209,138 @@ O3DX_HD inline int solve_update(const double* sums, double* upd) {
   return 1;
 }
 
+// ------------------------------------------------ point-to-point (Umeyama)
+// One-sided Jacobi rotation of columns I and J of G (3x3, row-major) and of
+// V, when they are not orthogonal to working precision.  Only + - * / sqrt:
+// the same bits on the host and the device.
+template <int I, int J>
+O3DX_HD inline bool jacobi_pair(double (&G)[9], double (&V)[9]) {
+  const double al = (G[I] * G[I] + G[3 + I] * G[3 + I]) + G[6 + I] * G[6 + I];
+  const double be = (G[J] * G[J] + G[3 + J] * G[3 + J]) + G[6 + J] * G[6 + J];
+  const double ga = (G[I] * G[J] + G[3 + I] * G[3 + J]) + G[6 + I] * G[6 + J];
+  // |g_I . g_J| <= 2^-53 |g_I| |g_J|: orthogonal
+  if (!(ga * ga > 1.232595164407831e-32 * (al * be))) return false;
+  const double zeta = (be - al) / (2.0 * ga);
+  const double az = fabs(zeta);
+  const double tt = 1.0 / (az + sqrt(1.0 + zeta * zeta));  // zeta^2 = inf: t = 0
+  const double t = zeta < 0.0 ? -tt : tt;
+  const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double gi = G[3 * k + I], gj = G[3 * k + J];
+    G[3 * k + I] = c * gi - s * gj;
+    G[3 * k + J] = s * gi + c * gj;
+    const double vi = V[3 * k + I], vj = V[3 * k + J];
+    V[3 * k + I] = c * vi - s * vj;
+    V[3 * k + J] = s * vi + c * vj;
+  }
+  return true;
+}
+
+// columns I and J of G and V (and their squared norms) exchanged when sw
+template <int I, int J>
+O3DX_HD inline void col_order(double (&G)[9], double (&V)[9], double (&n2)[3]) {
+  const bool sw = n2[J] > n2[I];
+  const double a = n2[I], b = n2[J];
+  n2[I] = sw ? b : a;
+  n2[J] = sw ? a : b;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const double gi = G[3 * k + I], gj = G[3 * k + J];
+    G[3 * k + I] = sw ? gj : gi;
+    G[3 * k + J] = sw ? gi : gj;
+    const double vi = V[3 * k + I], vj = V[3 * k + J];
+    V[3 * k + I] = sw ? vj : vi;
+    V[3 * k + J] = sw ? vi : vj;
+  }
+}
+
+// Eigen::umeyama's rotation of the 3x3 covariance A = U diag(s) V^T (s
+// descending): R = U diag(1, 1, d) V^T, d = -1 when det U det V < 0, and
+// *trace = s0 + s1 + d s2.  A one-sided Jacobi SVD: A V = G, the columns of G
+// orthogonal, |g_k| = s_k, u_k = g_k / s_k.  With u2' = u0 x u1 and v2' = v0
+// x v1 (= det U u2 and det V v2), d u2 v2^T = u2' v2'^T: R needs neither the
+// signs nor a division by the smallest singular value (an exactly planar set
+// has s2 = 0), and d s2 = (u2' . g2) (v2' . v2).  Every array index is a
+// constant, so on the device the matrices stay in registers.
+O3DX_HD inline void umeyama_rotation3(const double A[9], double R[9], double* trace) {
+  double G[9], V[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+#pragma unroll
+  for (int i = 0; i < 9; ++i) G[i] = A[i];
+  for (int sweep = 0; sweep < 30; ++sweep) {  // (converges in 4 .. 6 sweeps)
+    const bool r01 = jacobi_pair<0, 1>(G, V);
+    const bool r02 = jacobi_pair<0, 2>(G, V);
+    const bool r12 = jacobi_pair<1, 2>(G, V);
+    if (!(r01 || r02 || r12)) break;
+  }
+  double n2[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) n2[k] = (G[k] * G[k] + G[3 + k] * G[3 + k]) + G[6 + k] * G[6 + k];
+  col_order<0, 1>(G, V, n2);
+  col_order<0, 2>(G, V, n2);
+  col_order<1, 2>(G, V, n2);
+  const double s0 = sqrt(n2[0]), s1 = sqrt(n2[1]);
+  const double u0[3] = {G[0] / s0, G[3] / s0, G[6] / s0}, u1[3] = {G[1] / s1, G[4] / s1, G[7] / s1};
+  const double u2[3] = {u0[1] * u1[2] - u0[2] * u1[1], u0[2] * u1[0] - u0[0] * u1[2], u0[0] * u1[1] - u0[1] * u1[0]};
+  const double w2[3] = {V[3] * V[7] - V[6] * V[4], V[6] * V[1] - V[0] * V[7], V[0] * V[4] - V[3] * V[1]};
+#pragma unroll
+  for (int i = 0; i < 3; ++i)
+#pragma unroll
+    for (int j = 0; j < 3; ++j) R[3 * i + j] = (u0[i] * V[3 * j] + u1[i] * V[3 * j + 1]) + u2[i] * w2[j];
+  const double ug = (u2[0] * G[2] + u2[1] * G[5]) + u2[2] * G[8];
+  const double vv = (w2[0] * V[2] + w2[1] * V[5]) + w2[2] * V[8];
+  *trace = (s0 + s1) + ug * vv;
+}
+
+// The point-to-point update [cR | t] (Eigen::umeyama on the matched pairs)
+// from the anchored sums (include/o3dx.h, the point-to-point layout): p' = p -
+// a, q' = q - a about the anchor a = sums[16..18].  No matches, or a
+// non-finite result (with_scaling on a source of zero spread, a rank-1
+// covariance): the identity and 0, as solve_update.
+O3DX_HD inline int solve_update_p2p(const double* sums, int with_scaling, double* upd) {
+  const double n = sums[28];
+  bool ok = n > 0.0;
+  double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, t[3] = {0, 0, 0}, c = 1.0;
+  if (ok) {
+    double A[9], pm[3], qm[3], tr;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      pm[a] = sums[9 + a] / n;
+      qm[a] = sums[12 + a] / n;
+    }
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+      for (int b = 0; b < 3; ++b) A[3 * a + b] = (sums[3 * a + b] - sums[12 + a] * sums[9 + b] / n) / n;
+    const double sp2 = (sums[9] * sums[9] + sums[10] * sums[10]) + sums[11] * sums[11];
+    const double var = (sums[15] - sp2 / n) / n;
+    umeyama_rotation3(A, R, &tr);
+    if (with_scaling) c = var > 0.0 ? tr / var : NAN;  // (a zero spread can round below 0)
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+      const double pa0 = sums[16] + pm[0], pa1 = sums[17] + pm[1], pa2 = sums[18] + pm[2];
+      const double rp = (R[3 * i] * pa0 + R[3 * i + 1] * pa1) + R[3 * i + 2] * pa2;
+      t[i] = (sums[16 + i] + qm[i]) - c * rp;
+    }
+    ok = finite_d(c);
+#pragma unroll
+    for (int i = 0; i < 9; ++i) ok = ok && finite_d(R[i]);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ok = ok && finite_d(t[i]);
+  }
+  for (int a = 0; a < 16; ++a) upd[a] = (a % 5 == 0) ? 1.0 : 0.0;
+  if (!ok) return 0;
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) upd[4 * i + j] = c * R[3 * i + j];
+    upd[4 * i + 3] = t[i];
+  }
+  return 1;
+}
+
+O3DX_HD inline int solve_update_est(const double* sums, int est, int with_scaling, double* upd) {
+  return est == O3DX_ICP_POINT_TO_POINT ? solve_update_p2p(sums, with_scaling, upd) : solve_update(sums, upd);
+}
+
 O3DX_HD inline int fx_exp_hd(double B) {
   int e = 0;
   const double b = (B > 0.0 && B <= DBL_MAX) ? fmax(B, ldexp(1.0, -900)) : 1.0;
@@ -238,6 +377,27 @@ O3DX_HD inline void icp_fx_exps(const double absmax[3], const double* T, double 
   q[30] = q[31] = 0;
 }
 
+// Point-to-point: the moments are taken about a fixed anchor a, the target
+// grid's origin (p' = p - a, q' = q - a; moments about the coordinate origin
+// would cancel catastrophically on a cloud far from it).  A matched pair has
+//   |q'| <= D      the target grid box's diagonal (+ its slack): q is a target point
+//   |p'| <= D + max_corr     (|p - q| < max_corr)
+// whatever T and wherever the clouds lie, so the quanta depend on neither.
+// boxd: the box's extent per axis as seen from the anchor.
+O3DX_HD inline double icp_p2p_bound(const double boxd[3], double slack) {
+  return sqrt((boxd[0] * boxd[0] + boxd[1] * boxd[1]) + boxd[2] * boxd[2]) + slack;
+}
+O3DX_HD inline void icp_fx_exps_p2p(double D, double max_corr, int q[kNS]) {
+  const double bq = D * 1.01, bp = (D + max_corr) * 1.01;
+  for (int k = 0; k < 9; ++k) q[k] = fx_exp_hd(bq * bp * 1.01);
+  for (int k = 9; k < 12; ++k) q[k] = fx_exp_hd(bp);
+  for (int k = 12; k < 15; ++k) q[k] = fx_exp_hd(bq);
+  q[15] = fx_exp_hd(bp * bp * 1.01);
+  for (int k = 16; k < kNS; ++k) q[k] = 0;
+  q[28] = fx_exp_hd(1.0);
+  q[29] = fx_exp_hd(max_corr * max_corr * 1.01);
+}
+
 // fx_value: common.hpp
 
 O3DX_HD inline void icp_metrics(const double* sums, int64_t ns, double* fit, double* rm) {
@@ -264,12 +424,34 @@ struct IcpState {
   int32_t ext_on;    // the device loop: this step searches the extended ball (margins for the skip proof)
   int32_t ext_prev;  // ... and the previous one did (the margins are valid)
   int32_t wstop;     // the sharded loop: the new T leaves some rank's target window (the host refetches)
+  // point-to-point (appended: the fields above keep their offsets)
+  int32_t est;       // O3DX_ICP_POINT_TO_PLANE / O3DX_ICP_POINT_TO_POINT
+  double anchor[3];  // the moments' anchor (the target grid's origin)
+  double pD;         // icp_p2p_bound of the target grid
 };
 
-O3DX_HD inline void state_set_T(IcpState& st, const double* T, double max_corr) {
+O3DX_HD inline void state_set_T(IcpState& st, const double* T, double max_corr, int est = O3DX_ICP_POINT_TO_PLANE) {
   for (int i = 0; i < 16; ++i) st.Tp[i] = st.T[i];
   for (int i = 0; i < 16; ++i) st.T[i] = T[i];
-  icp_fx_exps(st.absmax, st.T, max_corr, st.q);
+  if (est == O3DX_ICP_POINT_TO_POINT) icp_fx_exps_p2p(st.pD, max_corr, st.q);
+  else icp_fx_exps(st.absmax, st.T, max_corr, st.q);
+}
+
+// the estimation of a state, with the anchor and bound of its target grid
+static void state_set_est(IcpState& st, int est, const GridView& g) {
+  st.est = est;
+  if (est != O3DX_ICP_POINT_TO_POINT) return;
+  const bool f64 = g.pts64 != nullptr;
+  // float64 grids: the anchor is the frame origin o64, the box starts at the
+  // frame's (ox, oy, oz)
+  const double o[3] = {g.ox, g.oy, g.oz}, o64[3] = {g.o64x, g.o64y, g.o64z};
+  const int nc[3] = {g.nx, g.ny, g.nz};
+  double boxd[3];
+  for (int a = 0; a < 3; ++a) {
+    st.anchor[a] = f64 ? o64[a] : o[a];
+    boxd[a] = (double)nc[a] * (double)g.h + (f64 ? std::fabs(o[a]) : 0.0);
+  }
+  st.pD = icp_p2p_bound(boxd, (double)g.slack);
 }
 
 struct Mat4 {
@@ -435,6 +617,27 @@ __device__ __forceinline__ int64_t icp_fx(const double (&J)[6], double r, double
   else
     return fx_term_q(icp_term<K>(J, r, d2, one), q[K]);
 }
+// point-to-point term k (include/o3dx.h, the point-to-point layout) of the
+// anchored pair P = p - a, Q = q - a: q'_a p'_b row-major, p', q', |p'|^2;
+// count and d^2 keep their slots (all zero for a lane without a match)
+template <int K>
+__device__ __forceinline__ int64_t icp_fx_p2p(const double (&P)[3], const double (&Q)[3], double d2, double one,
+                                              const int32_t* __restrict__ q) {
+  if constexpr (K < 9)
+    return fx_term_q(Q[K / 3] * P[K % 3], q[K]);
+  else if constexpr (K < 12)
+    return fx_term_q(P[K - 9], q[K]);
+  else if constexpr (K < 15)
+    return fx_term_q(Q[K - 12], q[K]);
+  else if constexpr (K == 15)
+    return fx_term_q((P[0] * P[0] + P[1] * P[1]) + P[2] * P[2], q[K]);
+  else if constexpr (K == 28)
+    return fx_term_q(one, q[K]);
+  else if constexpr (K == 29)
+    return fx_term_q(d2, q[K]);
+  else
+    return 0;
+}
 
 // block b -> a bijection on [0, nb) giving XCD x = b % 8 the contiguous run
 // [x q + min(x, r), ...) of the nb blocks (q = nb / 8, r = nb % 8)
@@ -473,7 +676,11 @@ __device__ __forceinline__ float float_down(double x) {
 // state's branch at run time instead of the two launches of which one returns
 // at once — 2700 against 2750 it/s at C3: the merged kernel's register
 // allocation costs the search steps more than the 9 us empty launch.)
-template <bool SORTED, bool F64 = false, int MODE = 0>
+// EST: the estimation.  Point-to-point reads no normal (tnorm may be null; the
+// match cache keeps the target point alone, mcb stays untouched) and forms
+// the 18 anchored Umeyama moments instead of the 30 point-to-plane ones; the
+// search, the skip proof and the reduction are the same.
+template <bool SORTED, bool F64 = false, int MODE = 0, int EST = O3DX_ICP_POINT_TO_PLANE>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MODE == 2 ? ICP_W2 : ICP_W1))) k_icp_step(const void* __restrict__ src, int64_t ns, GridView g,
                                                      const float4* __restrict__ tnorm,
                                                      const IcpState* __restrict__ st, double radius,
@@ -482,6 +689,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOD
                                                      double ext, float4* __restrict__ mca,
                                                      float2* __restrict__ mcb) {
   constexpr bool SKIP = MODE == 2;
+  constexpr bool P2P = EST == O3DX_ICP_POINT_TO_POINT;
   __shared__ int64_t sh[kBlock / 64][2 * kNS];
   if (st->done) return;  // converged: the loop's remaining steps do nothing
   if (MODE == 1 && st->ext_on) return;
@@ -527,7 +735,12 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOD
             cx = c.x;
             cy = c.y;
             cz = c.z;
-            cn = tnorm[mp];
+            if constexpr (!P2P) cn = tnorm[mp];
+          } else if constexpr (P2P) {
+            const float4 a = mca[j];
+            cx = a.x;
+            cy = a.y;
+            cz = a.z;
           } else {
             const float4 a = mca[j];
             const float2 bb = mcb[j];
@@ -553,7 +766,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOD
             vx = cx;
             vy = cy;
             vz = cz;
-            nt = cn;
+            if constexpr (!P2P) nt = cn;
             budget[j] = float_down(left);
           }
         }
@@ -580,18 +793,44 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOD
             vy = v.y;
             vz = v.z;
           }
-          nt = tnorm[pos];
+          if constexpr (!P2P) nt = tnorm[pos];
           if constexpr (SKIP && !F64) {  // the match cache of the next steps' skip proofs
             mca[j] = make_float4((float)vx, (float)vy, (float)vz, nt.x);
-            mcb[j] = make_float2(nt.y, nt.z);
+            if constexpr (!P2P) mcb[j] = make_float2(nt.y, nt.z);
           }
         }
       }
     }
     const bool m = pos >= 0;
-    double J[6] = {0, 0, 0, 0, 0, 0}, r = 0;
     const double one = m ? 1.0 : 0.0;
     if (!m) d2 = 0.0;
+    if constexpr (P2P) {
+      double P[3] = {0, 0, 0}, Q[3] = {0, 0, 0};
+      if (m) {
+        const double ax = st->anchor[0], ay = st->anchor[1], az = st->anchor[2];
+        P[0] = px - ax;
+        P[1] = py - ay;
+        P[2] = pz - az;
+        Q[0] = vx - ax;
+        Q[1] = vy - ay;
+        Q[2] = vz - az;
+      }
+      const int32_t* q = st->q;
+      {
+        const int64_t z = wave_transpose_sum16(
+            [&](auto ci) { return icp_fx_p2p<decltype(ci)::value>(P, Q, d2, one, q); }, lane);
+        alo[0] += z & 0xffffffffll;
+        ahi[0] += z >> 32;
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      {
+        const int64_t z = wave_transpose_sum16(
+            [&](auto ci) { return icp_fx_p2p<16 + decltype(ci)::value>(P, Q, d2, one, q); }, lane);
+        alo[1] += z & 0xffffffffll;
+        ahi[1] += z >> 32;
+      }
+    } else {
+    double J[6] = {0, 0, 0, 0, 0, 0}, r = 0;
     if (m) {
     const double nx = nt.x, ny = nt.y, nz = nt.z;
       r = ((px - vx) * nx + (py - vy) * ny) + (pz - vz) * nz;
@@ -615,6 +854,7 @@ __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MOD
           [&](auto ci) { return icp_fx<16 + decltype(ci)::value>(J, r, d2, one, q); }, lane);
       alo[1] += z & 0xffffffffll;
       ahi[1] += z >> 32;
+    }
     }
   }
   if ((lane & 3) == 0) {
@@ -694,12 +934,15 @@ __device__ inline bool windows_cover(const double* __restrict__ win, int world, 
 // the ranks), then (thread 0) the sums, fitness and rmse, Open3D's
 // convergence test against the previous iteration's, and — while iterations
 // remain — the solve and T <- update * T with the next fx exponents.
+// EST (a template parameter: the point-to-plane finish keeps its code and
+// registers) picks the solve; with_scaling is Umeyama's option.
+template <int EST = O3DX_ICP_POINT_TO_PLANE>
 __global__ void __launch_bounds__(1024) k_icp_finish(IcpState* __restrict__ st, int64_t* __restrict__ acc,
                                                      int64_t ns, double max_corr, double rel_fit, double rel_rmse,
                                                      int it, int max_it, double ext,
                                                      const int64_t* __restrict__ digits = nullptr,
                                                      const double* __restrict__ win = nullptr, int world = 0,
-                                                     double widen = 0.0) {
+                                                     double widen = 0.0, int with_scaling = 0) {
   __shared__ int64_t red[16][2 * kNS];
   __shared__ IcpState ls;
   __shared__ double sums[kNS];
@@ -722,6 +965,8 @@ __global__ void __launch_bounds__(1024) k_icp_finish(IcpState* __restrict__ st, 
   if (threadIdx.x == 0) {
     double sm[kNS];
     for (int k = 0; k < kNS; ++k) sm[k] = sums[k];
+    if constexpr (EST == O3DX_ICP_POINT_TO_POINT)
+      for (int a = 0; a < 3; ++a) sm[16 + a] = ls.anchor[a];
     double fit, rm;
     icp_metrics(sm, ns, &fit, &rm);
     const double pf = ls.fit, pr = ls.rmse;
@@ -732,7 +977,8 @@ __global__ void __launch_bounds__(1024) k_icp_finish(IcpState* __restrict__ st, 
       ls.done = 1;
     } else if (it < max_it) {
       double upd[16], T[16];
-      solve_update(sm, upd);
+      if constexpr (EST == O3DX_ICP_POINT_TO_POINT) solve_update_p2p(sm, with_scaling, upd);
+      else solve_update(sm, upd);
       mat4_mul(upd, ls.T, T);
       // the update's motion bound over the source box: |(T - T_old) p| per row
       double mv = 0.0;
@@ -741,7 +987,7 @@ __global__ void __launch_bounds__(1024) k_icp_finish(IcpState* __restrict__ st, 
                          fabs(T[4 * r + 2] - ls.T[4 * r + 2]) * ls.absmax[2] + fabs(T[4 * r + 3] - ls.T[4 * r + 3]);
         mv += e * e;
       }
-      state_set_T(ls, T, max_corr);
+      state_set_T(ls, T, max_corr, EST);
       ls.iters = it + 1;
       // the next step searches the extended ball (margins for the skip proof)
       // once the updates move the source by less than half of the extension:
@@ -799,7 +1045,8 @@ static void desc_pack(const GridBuild& G, const void* base, const float4* normal
   d[6] = g.nx; d[7] = g.ny; d[8] = g.nz; d[9] = (double)g.n;
   d[10] = (double)((const char*)G.pts - (const char*)base);
   d[11] = (double)((const char*)G.start - (const char*)base);
-  d[12] = (double)((const char*)normals - (const char*)base);
+  if (normals) d[12] = (double)((const char*)normals - (const char*)base);
+  else d[19] = 1;  // a target without normals (point-to-point only)
   d[13] = kDescMagic;
   if (G.pts64) {
     d[14] = (double)((const char*)G.pts64 - (const char*)base);
@@ -811,6 +1058,15 @@ static void desc_pack(const GridBuild& G, const void* base, const float4* normal
 }
 
 static bool desc_is_f64(const double* d) { return d && d[15] == 1; }
+static bool desc_no_normals(const double* d) { return d && d[13] == kDescMagic && d[19] == 1; }
+static bool est_known(int est) { return est == O3DX_ICP_POINT_TO_PLANE || est == O3DX_ICP_POINT_TO_POINT; }
+// the checks every entry with an estimation makes before any device call
+static int est_check(const char* who, int est, const double* desc) {
+  if (!est_known(est)) return fail(O3DX_EINVAL, "%s: unknown estimation %d", who, est);
+  if (est == O3DX_ICP_POINT_TO_PLANE && desc_no_normals(desc))
+    return fail(O3DX_EINVAL, "%s: point-to-plane needs a target built with normals", who);
+  return 0;
+}
 
 static bool desc_unpack(const double* d, const void* base, GridView* g, const float4** normals) {
   if (!d || d[13] != kDescMagic) return false;
@@ -823,7 +1079,7 @@ static bool desc_unpack(const double* d, const void* base, GridView* g, const fl
   g->bnx = g->bny = 0;
   g->pts = (const float4*)((const char*)base + (int64_t)d[10]);
   g->start = (const int32_t*)((const char*)base + (int64_t)d[11]);
-  *normals = (const float4*)((const char*)base + (int64_t)d[12]);
+  *normals = d[19] == 1 ? nullptr : (const float4*)((const char*)base + (int64_t)d[12]);
   if (desc_is_f64(d)) {
     g->pts64 = (const double4*)((const char*)base + (int64_t)d[14]);
     g->o64x = d[16];
@@ -957,19 +1213,25 @@ static int source_absmax(const void* src_, int64_t ns, bool sorted, AccWs& w, hi
 // searches cover a tenth of a cell beyond the match for the margin (measured:
 // h/16 .. h/8 within noise of each other, h/4 4 % and h/2 9 % slower at C3)
 static void launch_step(const void* src, int64_t ns, bool sorted, const GridView& g, const float4* tn,
-                        double radius, AccWs& w, hipStream_t s, int use_prior = 0, bool skip = false) {
+                        double radius, AccWs& w, hipStream_t s, int use_prior = 0, bool skip = false,
+                        int est = O3DX_ICP_POINT_TO_PLANE) {
   const unsigned nb = step_blocks(ns);
   const double ext = 0.1 * (double)g.h;
   KTimer km("icp_match", s);
-#define O3DX_STEP(SO, F6, MO)                                                                                     \
-  hipLaunchKernelGGL((k_icp_step<SO, F6, MO>), dim3(nb), dim3(kBlock), 0, s, src, ns, g, tn, w.st, radius, w.mpos, \
+#define O3DX_STEP(SO, F6, MO, ES)                                                                                     \
+  hipLaunchKernelGGL((k_icp_step<SO, F6, MO, ES>), dim3(nb), dim3(kBlock), 0, s, src, ns, g, tn, w.st, radius, w.mpos, \
                      use_prior, w.acc, w.budget, ext, w.mca, w.mcb)
-#define O3DX_STEPS(MO)                         \
-  do {                                         \
-    if (f64 && sorted) O3DX_STEP(true, true, MO);   \
-    else if (f64) O3DX_STEP(false, true, MO);       \
-    else if (sorted) O3DX_STEP(true, false, MO);    \
-    else O3DX_STEP(false, false, MO);               \
+#define O3DX_STEPS_E(MO, ES)                        \
+  do {                                              \
+    if (f64 && sorted) O3DX_STEP(true, true, MO, ES);   \
+    else if (f64) O3DX_STEP(false, true, MO, ES);       \
+    else if (sorted) O3DX_STEP(true, false, MO, ES);    \
+    else O3DX_STEP(false, false, MO, ES);               \
+  } while (0)
+#define O3DX_STEPS(MO)                                                                   \
+  do {                                                                                   \
+    if (est == O3DX_ICP_POINT_TO_POINT) O3DX_STEPS_E(MO, O3DX_ICP_POINT_TO_POINT);       \
+    else O3DX_STEPS_E(MO, O3DX_ICP_POINT_TO_PLANE);                                      \
   } while (0)
   const bool f64 = g.pts64 != nullptr;
   if (skip) {  // the state picks one of the two at run time
@@ -979,6 +1241,7 @@ static void launch_step(const void* src, int64_t ns, bool sorted, const GridView
     O3DX_STEPS(0);
   }
 #undef O3DX_STEPS
+#undef O3DX_STEPS_E
 #undef O3DX_STEP
 }
 // correspondences of the last step into corr_out (pairs by original index)
@@ -1013,15 +1276,16 @@ static int corr_of_last_step(const void* src, int64_t ns, bool sorted, const Gri
 // of a sharded source; fx_out (nullable, host 4 x kNS): the exact sums.
 static int accumulate(const void* src, int64_t ns, bool sorted, const GridView& g, const float4* tn, const double* T,
                       double radius, const double* absmax, AccWs& w, hipStream_t s, double* sums_host,
-                      int64_t* fx_out, int32_t* corr_out, int64_t* ncorr) {
+                      int64_t* fx_out, int32_t* corr_out, int64_t* ncorr, int est = O3DX_ICP_POINT_TO_PLANE) {
   IcpState hs{};
   for (int a = 0; a < 3; ++a) hs.absmax[a] = absmax[a];
-  state_set_T(hs, T, radius);
+  state_set_est(hs, est, g);
+  state_set_T(hs, T, radius, est);
   KTimer kt("icp_accumulate", s);
   if (ns > 0) {
     O3DX_HIP(hipMemcpyAsync(w.st, &hs, sizeof(IcpState), hipMemcpyHostToDevice, s));
     O3DX_HIP(hipMemsetAsync(w.acc, 0, (size_t)kIcpCopies * 2 * kNS * sizeof(int64_t), s));
-    launch_step(src, ns, sorted, g, tn, radius, w, s);
+    launch_step(src, ns, sorted, g, tn, radius, w, s, 0, false, est);
     hipLaunchKernelGGL(k_icp_collect, dim3(1), dim3(1024), 0, s, w.acc, w.digits);
   } else {
     O3DX_HIP(hipMemsetAsync(w.digits, 0, 2 * kNS * sizeof(int64_t), s));
@@ -1032,8 +1296,17 @@ static int accumulate(const void* src, int64_t ns, bool sorted, const GridView& 
   int64_t digits[2 * kNS], fx[4 * kNS];
   O3DX_TRY(read_back(digits, w.digits, sizeof(digits), s));
   O3DX_HIP(hipGetLastError());
+  if (est == O3DX_ICP_POINT_TO_POINT)
+    // the carry of the low digits moved up: the rows {lo < 2^32, hi} are then
+    // the same for any order of the source, not only the values they stand for
+    for (int k = 0; k < kNS; ++k) {
+      digits[2 * k + 1] += digits[2 * k] >> 32;
+      digits[2 * k] &= 0xffffffffll;
+    }
   fx_pack(digits, hs.q, kNS, fx);
   for (int k = 0; k < kNS; ++k) sums_host[k] = k < kNT ? fx_value(digits[2 * k], digits[2 * k + 1], hs.q[k]) : 0.0;
+  if (est == O3DX_ICP_POINT_TO_POINT)  // the anchor travels with the sums (its digits are 0)
+    for (int a = 0; a < 3; ++a) sums_host[16 + a] = hs.anchor[a];
   if (fx_out) std::memcpy(fx_out, fx, sizeof(fx));
   if (ncorr && !corr_out) *ncorr = (int64_t)sums_host[28];
   return 0;
@@ -1054,17 +1327,29 @@ using namespace o3dx;
 
 extern "C" size_t o3dx_icp_target_workspace_bytes(int64_t nt) { return grid_ws_bytes(nt, icp_cap_mult()) + 1024; }
 
-extern "C" int o3dx_icp_target_build(const float* tgt, const float* tgt_normals, int64_t nt, double max_corr,
-                                     void* target_ws, size_t target_ws_bytes, double* desc, void* stream) {
-  if (nt < 0 || (nt > 0 && (!tgt || !tgt_normals)) || !desc) return fail(O3DX_EINVAL, "o3dx_icp_target_build: bad args");
+// tgt_normals null: a target without normals (o3dx_icp_target_build_points)
+static int target_build(const float* tgt, const float* tgt_normals, int64_t nt, double max_corr, void* target_ws,
+                        size_t target_ws_bytes, double* desc, void* stream) {
   if (!(max_corr > 0.0)) return fail(O3DX_EINVAL, "max_correspondence_distance must be > 0");
   if (!target_ws || target_ws_bytes < o3dx_icp_target_workspace_bytes(nt))
     return fail(O3DX_ENOMEM, "icp target workspace too small");
   GridBuild G;
   O3DX_TRY(grid_build(tgt, nt, icp_occ(), icp_min_h(max_corr), target_ws, target_ws_bytes, as_stream(stream), &G, nullptr,
                       tgt_normals, false, icp_cap_mult()));
-  desc_pack(G, target_ws, G.extra, desc);
+  desc_pack(G, target_ws, tgt_normals ? G.extra : nullptr, desc);
   return 0;
+}
+
+extern "C" int o3dx_icp_target_build(const float* tgt, const float* tgt_normals, int64_t nt, double max_corr,
+                                     void* target_ws, size_t target_ws_bytes, double* desc, void* stream) {
+  if (nt < 0 || (nt > 0 && (!tgt || !tgt_normals)) || !desc) return fail(O3DX_EINVAL, "o3dx_icp_target_build: bad args");
+  return target_build(tgt, tgt_normals, nt, max_corr, target_ws, target_ws_bytes, desc, stream);
+}
+
+extern "C" int o3dx_icp_target_build_points(const float* tgt, int64_t nt, double max_corr, void* target_ws,
+                                            size_t target_ws_bytes, double* desc, void* stream) {
+  if (nt < 0 || (nt > 0 && !tgt) || !desc) return fail(O3DX_EINVAL, "o3dx_icp_target_build_points: bad args");
+  return target_build(tgt, nullptr, nt, max_corr, target_ws, target_ws_bytes, desc, stream);
 }
 
 extern "C" size_t o3dx_icp_accumulate_workspace_bytes(int64_t ns) {
@@ -1073,10 +1358,11 @@ extern "C" size_t o3dx_icp_accumulate_workspace_bytes(int64_t ns) {
   return acc_carve(ar, std::max<int64_t>(ns, 1), &w) + 1024;
 }
 
-extern "C" int o3dx_icp_accumulate(const float* src, int64_t ns, int src_sorted4, const void* target_ws,
-                                   const double* desc, const double* T, double max_corr, const double* src_absmax,
-                                   double* sums, int64_t* fx_out, int32_t* corr_out, int64_t* ncorr, void* ws,
-                                   size_t ws_bytes, void* stream) {
+extern "C" int o3dx_icp_accumulate_est(const float* src, int64_t ns, int src_sorted4, const void* target_ws,
+                                       const double* desc, const double* T, double max_corr,
+                                       const double* src_absmax, double* sums, int64_t* fx_out, int32_t* corr_out,
+                                       int64_t* ncorr, int estimation, void* ws, size_t ws_bytes, void* stream) {
+  O3DX_TRY(est_check("o3dx_icp_accumulate", estimation, desc));
   if (ns < 0 || (ns > 0 && !src) || !target_ws || !T || !sums) return fail(O3DX_EINVAL, "o3dx_icp_accumulate: bad args");
   if (desc_is_f64(desc)) return fail(O3DX_EINVAL, "a float64 ICP target takes a float64 source (o3dx_icp_register_f64)");
   GridView g;
@@ -1090,7 +1376,16 @@ extern "C" int o3dx_icp_accumulate(const float* src, int64_t ns, int src_sorted4
   double am[3] = {0, 0, 0};
   if (src_absmax) std::memcpy(am, src_absmax, sizeof(am));
   else if (ns > 0) O3DX_TRY(source_absmax(src, ns, src_sorted4 != 0, w, s, am));
-  return accumulate(src, ns, src_sorted4 != 0, g, tn, T, max_corr, am, w, s, sums, fx_out, corr_out, ncorr);
+  return accumulate(src, ns, src_sorted4 != 0, g, tn, T, max_corr, am, w, s, sums, fx_out, corr_out, ncorr,
+                    estimation);
+}
+
+extern "C" int o3dx_icp_accumulate(const float* src, int64_t ns, int src_sorted4, const void* target_ws,
+                                   const double* desc, const double* T, double max_corr, const double* src_absmax,
+                                   double* sums, int64_t* fx_out, int32_t* corr_out, int64_t* ncorr, void* ws,
+                                   size_t ws_bytes, void* stream) {
+  return o3dx_icp_accumulate_est(src, ns, src_sorted4, target_ws, desc, T, max_corr, src_absmax, sums, fx_out,
+                                 corr_out, ncorr, O3DX_ICP_POINT_TO_PLANE, ws, ws_bytes, stream);
 }
 
 extern "C" size_t o3dx_spatial_sort_workspace_bytes(int64_t n) { return grid_ws_bytes(n) + 1024; }
@@ -1133,6 +1428,20 @@ extern "C" int o3dx_icp_update(const double* sums, double* T) {
   return solved;
 }
 
+extern "C" int o3dx_icp_solve_point_to_point(const double* sums, int with_scaling, double* upd) {
+  if (!sums || !upd) return fail(O3DX_EINVAL, "o3dx_icp_solve_point_to_point: bad args");
+  return solve_update_p2p(sums, with_scaling != 0, upd);
+}
+
+extern "C" int o3dx_icp_update_est(const double* sums, int estimation, int with_scaling, double* T) {
+  O3DX_TRY(est_check("o3dx_icp_update_est", estimation, nullptr));
+  if (!sums || !T) return fail(O3DX_EINVAL, "o3dx_icp_update_est: bad args");
+  double upd[16];
+  const int solved = solve_update_est(sums, estimation, with_scaling != 0, upd);
+  mat4_mul(upd, T, T);
+  return solved;
+}
+
 extern "C" size_t o3dx_registration_icp_workspace_bytes(int64_t ns) {
   ns = std::max<int64_t>(ns, 1);
   return Arena::align((size_t)ns * sizeof(float4) + 1) +
@@ -1144,7 +1453,8 @@ extern "C" size_t o3dx_registration_icp_workspace_bytes(int64_t ns) {
 // instruction); the host waits once for the final state.
 static int run_loop(const void* src, int64_t ns, bool sorted, const GridView& g, const float4* tn, double max_corr, const double* init, int max_iteration, double rel_fit,
                     double rel_rmse, const double* absmax, AccWs& w, hipStream_t s, double* T_out, double* fitness,
-                    double* rmse, int32_t* corr_out, int64_t* ncorr) {
+                    double* rmse, int32_t* corr_out, int64_t* ncorr, int est = O3DX_ICP_POINT_TO_PLANE,
+                    int with_scaling = 0) {
   IcpState hs{};
   double T0[16];
   if (init) std::memcpy(T0, init, sizeof(T0));
@@ -1159,7 +1469,8 @@ static int run_loop(const void* src, int64_t ns, bool sorted, const GridView& g,
   }
   if (absmax) std::memcpy(hs.absmax, absmax, sizeof(hs.absmax));
   else O3DX_TRY(source_absmax(src, ns, sorted, w, s, hs.absmax, g.pts64 != nullptr));
-  state_set_T(hs, T0, max_corr);
+  state_set_est(hs, est, g);
+  state_set_T(hs, T0, max_corr, est);
   O3DX_HIP(hipMemcpyAsync(w.st, &hs, sizeof(IcpState), hipMemcpyHostToDevice, s));
   O3DX_HIP(hipMemsetAsync(w.acc, 0, (size_t)kIcpCopies * 2 * kNS * sizeof(int64_t), s));
   const int iters = std::max(max_iteration, 0);
@@ -1169,9 +1480,15 @@ static int run_loop(const void* src, int64_t ns, bool sorted, const GridView& g,
     KTimer kt("icp_loop", s);
     for (int it = 0; it <= iters; ++it) {
       // from the second step on, the previous step's matches seed the search
-      launch_step(src, ns, sorted, g, tn, max_corr, w, s, it > 0, skip);
-      hipLaunchKernelGGL(k_icp_finish, dim3(1), dim3(1024), 0, s, w.st, w.acc, ns, max_corr, rel_fit, rel_rmse, it,
-                         iters, skip ? 0.1 * (double)g.h : 0.0);
+      launch_step(src, ns, sorted, g, tn, max_corr, w, s, it > 0, skip, est);
+      const double ext = skip ? 0.1 * (double)g.h : 0.0;
+      if (est == O3DX_ICP_POINT_TO_POINT)
+        hipLaunchKernelGGL(k_icp_finish<O3DX_ICP_POINT_TO_POINT>, dim3(1), dim3(1024), 0, s, w.st, w.acc, ns, max_corr,
+                           rel_fit, rel_rmse, it, iters, ext, (const int64_t*)nullptr, (const double*)nullptr, 0, 0.0,
+                           with_scaling);
+      else
+        hipLaunchKernelGGL(k_icp_finish<>, dim3(1), dim3(1024), 0, s, w.st, w.acc, ns, max_corr, rel_fit, rel_rmse, it,
+                           iters, ext);
     }
   }
   O3DX_HIP(hipGetLastError());
@@ -1184,11 +1501,12 @@ static int run_loop(const void* src, int64_t ns, bool sorted, const GridView& g,
   return 0;
 }
 
-extern "C" int o3dx_icp_register(const float* src, int64_t ns, int src_sorted4, const void* target_ws,
-                                 const double* desc, const double* init, int max_iteration, double rel_fit,
-                                 double rel_rmse, double max_corr, const double* src_absmax, double* T_out,
-                                 double* fitness, double* rmse, int32_t* corr_out, int64_t* ncorr, void* ws,
-                                 size_t ws_bytes, void* stream) {
+extern "C" int o3dx_icp_register_est(const float* src, int64_t ns, int src_sorted4, const void* target_ws,
+                                     const double* desc, const double* init, int max_iteration, double rel_fit,
+                                     double rel_rmse, double max_corr, const double* src_absmax, double* T_out,
+                                     double* fitness, double* rmse, int32_t* corr_out, int64_t* ncorr,
+                                     int estimation, int with_scaling, void* ws, size_t ws_bytes, void* stream) {
+  O3DX_TRY(est_check("o3dx_icp_register", estimation, desc));
   if (ns < 0 || (ns > 0 && !src) || !target_ws || !T_out || !fitness || !rmse)
     return fail(O3DX_EINVAL, "o3dx_icp_register: bad args");
   if (!(max_corr > 0.0)) return fail(O3DX_EINVAL, "max_correspondence_distance must be > 0");
@@ -1201,7 +1519,17 @@ extern "C" int o3dx_icp_register(const float* src, int64_t ns, int src_sorted4, 
   AccWs w;
   acc_carve(ar, std::max<int64_t>(ns, 1), &w);
   return run_loop(src, ns, src_sorted4 != 0, g, tn, max_corr, init, max_iteration, rel_fit, rel_rmse, src_absmax,
-                  w, as_stream(stream), T_out, fitness, rmse, corr_out, ncorr);
+                  w, as_stream(stream), T_out, fitness, rmse, corr_out, ncorr, estimation, with_scaling != 0);
+}
+
+extern "C" int o3dx_icp_register(const float* src, int64_t ns, int src_sorted4, const void* target_ws,
+                                 const double* desc, const double* init, int max_iteration, double rel_fit,
+                                 double rel_rmse, double max_corr, const double* src_absmax, double* T_out,
+                                 double* fitness, double* rmse, int32_t* corr_out, int64_t* ncorr, void* ws,
+                                 size_t ws_bytes, void* stream) {
+  return o3dx_icp_register_est(src, ns, src_sorted4, target_ws, desc, init, max_iteration, rel_fit, rel_rmse, max_corr,
+                               src_absmax, T_out, fitness, rmse, corr_out, ncorr, O3DX_ICP_POINT_TO_PLANE, 0, ws,
+                               ws_bytes, stream);
 }
 
 // ------------------------------------------------ the sharded device loop
@@ -1264,6 +1592,7 @@ extern "C" int o3dx_icp_shard_step(const float* src, int64_t ns, int src_sorted4
     return 0;
   }
   if (desc_is_f64(desc)) return fail(O3DX_EINVAL, "o3dx_icp_shard_step: float32 targets only");
+  O3DX_TRY(est_check("o3dx_icp_shard_step", O3DX_ICP_POINT_TO_PLANE, desc));
   GridView g;
   const float4* tn;
   if (!desc_unpack(desc, target_ws, &g, &tn)) return fail(O3DX_EINVAL, "invalid ICP target descriptor");
@@ -1284,7 +1613,7 @@ extern "C" int o3dx_icp_shard_finish(const int64_t* digits_dev, int64_t n_total,
   // the skip proof's extension of this rank's target grid (0: no target here)
   const double ext =
       (desc && desc[13] == kDescMagic && icp_skip_on() && 0.1 * (double)(float)desc[3] <= widen) ? 0.1 * (double)(float)desc[3] : 0.0;
-  hipLaunchKernelGGL(k_icp_finish, dim3(1), dim3(1024), 0, as_stream(stream), w.st, w.acc, std::max<int64_t>(n_total, 1),
+  hipLaunchKernelGGL(k_icp_finish<>, dim3(1), dim3(1024), 0, as_stream(stream), w.st, w.acc, std::max<int64_t>(n_total, 1),
                      max_corr, rel_fit, rel_rmse, it, std::max(max_iteration, 0), ext, digits_dev, win_dev, world,
                      widen);
   O3DX_HIP(hipGetLastError());
@@ -1323,18 +1652,22 @@ extern "C" int o3dx_icp_shard_resume(int64_t ns, void* ws, size_t ws_bytes, void
   return 0;
 }
 
-extern "C" int o3dx_registration_icp_point_to_plane(const float* src, int64_t ns, const float* tgt,
-                                                    const float* tgt_normals, int64_t nt, double max_corr,
-                                                    const double* init, int max_iteration, double rel_fit,
-                                                    double rel_rmse, double* T_out, double* fitness, double* rmse,
-                                                    int32_t* corr_out, int64_t* ncorr, void* target_ws,
-                                                    size_t target_ws_bytes, void* ws, size_t ws_bytes, void* stream) {
+extern "C" int o3dx_registration_icp_est(const float* src, int64_t ns, const float* tgt, const float* tgt_normals,
+                                         int64_t nt, double max_corr, const double* init, int max_iteration,
+                                         double rel_fit, double rel_rmse, double* T_out, double* fitness,
+                                         double* rmse, int32_t* corr_out, int64_t* ncorr, int estimation,
+                                         int with_scaling, void* target_ws, size_t target_ws_bytes, void* ws,
+                                         size_t ws_bytes, void* stream) {
+  O3DX_TRY(est_check("o3dx_registration_icp", estimation, nullptr));
   if (!T_out || !fitness || !rmse) return fail(O3DX_EINVAL, "registration_icp: bad args");
   if (!(max_corr > 0.0)) return fail(O3DX_EINVAL, "max_correspondence_distance must be > 0");
   if (ns < 0 || (ns > 0 && !src)) return fail(O3DX_EINVAL, "registration_icp: bad args");
   hipStream_t s = as_stream(stream);
   double desc[O3DX_ICP_DESC_LEN];
-  O3DX_TRY(o3dx_icp_target_build(tgt, tgt_normals, nt, max_corr, target_ws, target_ws_bytes, desc, stream));
+  if (estimation == O3DX_ICP_POINT_TO_POINT && !tgt_normals)
+    O3DX_TRY(o3dx_icp_target_build_points(tgt, nt, max_corr, target_ws, target_ws_bytes, desc, stream));
+  else
+    O3DX_TRY(o3dx_icp_target_build(tgt, tgt_normals, nt, max_corr, target_ws, target_ws_bytes, desc, stream));
   GridView g;
   const float4* tn;
   desc_unpack(desc, target_ws, &g, &tn);
@@ -1349,7 +1682,18 @@ extern "C" int o3dx_registration_icp_point_to_plane(const float* src, int64_t ns
   AccWs w;
   acc_carve(ar, std::max<int64_t>(ns, 1), &w);
   return run_loop(src4, ns, true, g, tn, max_corr, init, max_iteration, rel_fit, rel_rmse, am, w, s, T_out,
-                  fitness, rmse, corr_out, ncorr);
+                  fitness, rmse, corr_out, ncorr, estimation, with_scaling != 0);
+}
+
+extern "C" int o3dx_registration_icp_point_to_plane(const float* src, int64_t ns, const float* tgt,
+                                                    const float* tgt_normals, int64_t nt, double max_corr,
+                                                    const double* init, int max_iteration, double rel_fit,
+                                                    double rel_rmse, double* T_out, double* fitness, double* rmse,
+                                                    int32_t* corr_out, int64_t* ncorr, void* target_ws,
+                                                    size_t target_ws_bytes, void* ws, size_t ws_bytes, void* stream) {
+  return o3dx_registration_icp_est(src, ns, tgt, tgt_normals, nt, max_corr, init, max_iteration, rel_fit, rel_rmse,
+                                   T_out, fitness, rmse, corr_out, ncorr, O3DX_ICP_POINT_TO_PLANE, 0, target_ws,
+                                   target_ws_bytes, ws, ws_bytes, stream);
 }
 
 // ------------------------------------------------------ float64 boundary
@@ -1363,18 +1707,29 @@ extern "C" size_t o3dx_icp_target_f64_workspace_bytes(int64_t nt) {
   return grid64_ws_bytes(nt, icp_cap_mult()) + 1024;
 }
 
-extern "C" int o3dx_icp_target_build_f64(const double* tgt, const float* tgt_normals, int64_t nt, double max_corr,
-                                         void* target_ws, size_t target_ws_bytes, double* desc, void* stream) {
-  if (nt < 0 || (nt > 0 && (!tgt || !tgt_normals)) || !desc)
-    return fail(O3DX_EINVAL, "o3dx_icp_target_build_f64: bad args");
+static int target_build_f64(const double* tgt, const float* tgt_normals, int64_t nt, double max_corr,
+                            void* target_ws, size_t target_ws_bytes, double* desc, void* stream) {
   if (!(max_corr > 0.0)) return fail(O3DX_EINVAL, "max_correspondence_distance must be > 0");
   if (!target_ws || target_ws_bytes < o3dx_icp_target_f64_workspace_bytes(nt))
     return fail(O3DX_ENOMEM, "icp target workspace too small");
   GridBuild G;
   O3DX_TRY(grid64_build(tgt, nt, icp_occ(), icp_min_h(max_corr), target_ws, target_ws_bytes, as_stream(stream), &G,
                         tgt_normals, icp_cap_mult()));
-  desc_pack(G, target_ws, G.extra, desc);
+  desc_pack(G, target_ws, tgt_normals ? G.extra : nullptr, desc);
   return 0;
+}
+
+extern "C" int o3dx_icp_target_build_f64(const double* tgt, const float* tgt_normals, int64_t nt, double max_corr,
+                                         void* target_ws, size_t target_ws_bytes, double* desc, void* stream) {
+  if (nt < 0 || (nt > 0 && (!tgt || !tgt_normals)) || !desc)
+    return fail(O3DX_EINVAL, "o3dx_icp_target_build_f64: bad args");
+  return target_build_f64(tgt, tgt_normals, nt, max_corr, target_ws, target_ws_bytes, desc, stream);
+}
+
+extern "C" int o3dx_icp_target_build_points_f64(const double* tgt, int64_t nt, double max_corr, void* target_ws,
+                                                size_t target_ws_bytes, double* desc, void* stream) {
+  if (nt < 0 || (nt > 0 && !tgt) || !desc) return fail(O3DX_EINVAL, "o3dx_icp_target_build_points_f64: bad args");
+  return target_build_f64(tgt, nullptr, nt, max_corr, target_ws, target_ws_bytes, desc, stream);
 }
 
 extern "C" size_t o3dx_spatial_sort_f64_workspace_bytes(int64_t n) { return grid64_ws_bytes(n) + 1024; }
@@ -1395,11 +1750,12 @@ extern "C" int o3dx_spatial_sort_f64(const double* xyz, int64_t n, double target
   return 0;
 }
 
-extern "C" int o3dx_icp_register_f64(const double* src, int64_t ns, int src_sorted4, const void* target_ws,
-                                     const double* desc, const double* init, int max_iteration, double rel_fit,
-                                     double rel_rmse, double max_corr, const double* src_absmax, double* T_out,
-                                     double* fitness, double* rmse, int32_t* corr_out, int64_t* ncorr, void* ws,
-                                     size_t ws_bytes, void* stream) {
+extern "C" int o3dx_icp_register_est_f64(const double* src, int64_t ns, int src_sorted4, const void* target_ws,
+                                         const double* desc, const double* init, int max_iteration, double rel_fit,
+                                         double rel_rmse, double max_corr, const double* src_absmax, double* T_out,
+                                         double* fitness, double* rmse, int32_t* corr_out, int64_t* ncorr,
+                                         int estimation, int with_scaling, void* ws, size_t ws_bytes, void* stream) {
+  O3DX_TRY(est_check("o3dx_icp_register_f64", estimation, desc));
   if (ns < 0 || (ns > 0 && !src) || !target_ws || !T_out || !fitness || !rmse)
     return fail(O3DX_EINVAL, "o3dx_icp_register_f64: bad args");
   if (!(max_corr > 0.0)) return fail(O3DX_EINVAL, "max_correspondence_distance must be > 0");
@@ -1412,7 +1768,17 @@ extern "C" int o3dx_icp_register_f64(const double* src, int64_t ns, int src_sort
   AccWs w;
   acc_carve(ar, std::max<int64_t>(ns, 1), &w);
   return run_loop(src, ns, src_sorted4 != 0, g, tn, max_corr, init, max_iteration, rel_fit, rel_rmse, src_absmax,
-                  w, as_stream(stream), T_out, fitness, rmse, corr_out, ncorr);
+                  w, as_stream(stream), T_out, fitness, rmse, corr_out, ncorr, estimation, with_scaling != 0);
+}
+
+extern "C" int o3dx_icp_register_f64(const double* src, int64_t ns, int src_sorted4, const void* target_ws,
+                                     const double* desc, const double* init, int max_iteration, double rel_fit,
+                                     double rel_rmse, double max_corr, const double* src_absmax, double* T_out,
+                                     double* fitness, double* rmse, int32_t* corr_out, int64_t* ncorr, void* ws,
+                                     size_t ws_bytes, void* stream) {
+  return o3dx_icp_register_est_f64(src, ns, src_sorted4, target_ws, desc, init, max_iteration, rel_fit, rel_rmse,
+                                   max_corr, src_absmax, T_out, fitness, rmse, corr_out, ncorr,
+                                   O3DX_ICP_POINT_TO_PLANE, 0, ws, ws_bytes, stream);
 }
 
 extern "C" size_t o3dx_registration_icp_f64_workspace_bytes(int64_t ns) {
@@ -1421,19 +1787,22 @@ extern "C" size_t o3dx_registration_icp_f64_workspace_bytes(int64_t ns) {
          std::max(o3dx_icp_accumulate_workspace_bytes(ns), o3dx_spatial_sort_f64_workspace_bytes(ns)) + 1024;
 }
 
-extern "C" int o3dx_registration_icp_point_to_plane_f64(const double* src, int64_t ns, const double* tgt,
-                                                        const float* tgt_normals, int64_t nt, double max_corr,
-                                                        const double* init, int max_iteration, double rel_fit,
-                                                        double rel_rmse, double* T_out, double* fitness, double* rmse,
-                                                        int32_t* corr_out, int64_t* ncorr, void* target_ws,
-                                                        size_t target_ws_bytes, void* ws, size_t ws_bytes,
-                                                        void* stream) {
+extern "C" int o3dx_registration_icp_est_f64(const double* src, int64_t ns, const double* tgt,
+                                             const float* tgt_normals, int64_t nt, double max_corr,
+                                             const double* init, int max_iteration, double rel_fit, double rel_rmse,
+                                             double* T_out, double* fitness, double* rmse, int32_t* corr_out,
+                                             int64_t* ncorr, int estimation, int with_scaling, void* target_ws,
+                                             size_t target_ws_bytes, void* ws, size_t ws_bytes, void* stream) {
+  O3DX_TRY(est_check("o3dx_registration_icp_f64", estimation, nullptr));
   if (!T_out || !fitness || !rmse) return fail(O3DX_EINVAL, "registration_icp_f64: bad args");
   if (!(max_corr > 0.0)) return fail(O3DX_EINVAL, "max_correspondence_distance must be > 0");
   if (ns < 0 || (ns > 0 && !src)) return fail(O3DX_EINVAL, "registration_icp_f64: bad args");
   hipStream_t s = as_stream(stream);
   double desc[O3DX_ICP_DESC_LEN];
-  O3DX_TRY(o3dx_icp_target_build_f64(tgt, tgt_normals, nt, max_corr, target_ws, target_ws_bytes, desc, stream));
+  if (estimation == O3DX_ICP_POINT_TO_POINT && !tgt_normals)
+    O3DX_TRY(o3dx_icp_target_build_points_f64(tgt, nt, max_corr, target_ws, target_ws_bytes, desc, stream));
+  else
+    O3DX_TRY(o3dx_icp_target_build_f64(tgt, tgt_normals, nt, max_corr, target_ws, target_ws_bytes, desc, stream));
   GridView g;
   const float4* tn;
   desc_unpack(desc, target_ws, &g, &tn);
@@ -1446,5 +1815,17 @@ extern "C" int o3dx_registration_icp_point_to_plane_f64(const double* src, int64
   AccWs w;
   acc_carve(ar, std::max<int64_t>(ns, 1), &w);
   return run_loop(src4, ns, true, g, tn, max_corr, init, max_iteration, rel_fit, rel_rmse, nullptr, w, s, T_out,
-                  fitness, rmse, corr_out, ncorr);
+                  fitness, rmse, corr_out, ncorr, estimation, with_scaling != 0);
+}
+
+extern "C" int o3dx_registration_icp_point_to_plane_f64(const double* src, int64_t ns, const double* tgt,
+                                                        const float* tgt_normals, int64_t nt, double max_corr,
+                                                        const double* init, int max_iteration, double rel_fit,
+                                                        double rel_rmse, double* T_out, double* fitness, double* rmse,
+                                                        int32_t* corr_out, int64_t* ncorr, void* target_ws,
+                                                        size_t target_ws_bytes, void* ws, size_t ws_bytes,
+                                                        void* stream) {
+  return o3dx_registration_icp_est_f64(src, ns, tgt, tgt_normals, nt, max_corr, init, max_iteration, rel_fit,
+                                       rel_rmse, T_out, fitness, rmse, corr_out, ncorr, O3DX_ICP_POINT_TO_PLANE, 0,
+                                       target_ws, target_ws_bytes, ws, ws_bytes, stream);
 }

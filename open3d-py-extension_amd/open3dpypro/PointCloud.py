@@ -31,7 +31,7 @@ import torch
 
 from . import ops, pcd_io
 from . import _native as N
-from .params import KDTreeSearchParamKNN, resolve
+from .params import KDTreeSearchParamKNN, resolve, resolve_estimation
 
 _SEED = [None]
 
@@ -931,11 +931,20 @@ class PointCloud(PointCloudUtility):
         return pcds, lab.cpu().numpy().astype(np.int64)
 
     def registration_icp(self, target: "PointCloudBase", max_correspondence_distance: float, init=None,
-                         max_iteration: int = 30, relative_fitness: float = 1e-6, relative_rmse: float = 1e-6):
-        """Point-to-plane ICP of self onto target (Open3D registration_icp with
-        TransformationEstimationPointToPlane), on the GPU.  North-star op; the
+                         max_iteration: int = 30, relative_fitness: float = 1e-6, relative_rmse: float = 1e-6,
+                         estimation="point_to_plane"):
+        """ICP of self onto target (Open3D registration_icp), on the GPU.
+        estimation: "point_to_plane" (TransformationEstimationPointToPlane; the
+        target needs normals) or "point_to_point"
+        (TransformationEstimationPointToPoint, Umeyama; no normals needed), or
+        one of the params.TransformationEstimation* objects (PointToPoint's
+        with_scaling included).  NOTE: the default here is point-to-plane,
+        where Open3D's registration_icp defaults to point-to-point — pass the
+        estimation explicitly when porting a call that relies on Open3D's
+        default.  ValueError on any other estimation.  North-star op; the
         reference has no ICP."""
-        if not target.has_normals():
+        est, with_scaling = resolve_estimation(estimation)
+        if est == "point_to_plane" and not target.has_normals():
             raise RuntimeError("TransformationEstimationPointToPlane and TransformationEstimationColoredICP "
                                "require pre-computed normal vectors for target PointCloud.")
         if max_correspondence_distance <= 0.0:
@@ -943,9 +952,10 @@ class PointCloud(PointCloudUtility):
         wide = self._wide or target._wide
         src = self._plane_points() if wide else self._dev_points()
         tgt = target._plane_points() if wide else target._dev_points()
-        if wide:
+        if wide and est == "point_to_plane":
             _warn_offset_icp(self, target)
-        r = ops.registration_icp(src, tgt, target._normals,
-                                 max_correspondence_distance, init, max_iteration, relative_fitness, relative_rmse)
+        r = ops.registration_icp(src, tgt, target._normals if target.has_normals() else None,
+                                 max_correspondence_distance, init, max_iteration, relative_fitness, relative_rmse,
+                                 estimation=est, with_scaling=with_scaling)
         return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"],
                                   r["correspondence_set"].cpu().numpy().astype(np.int64))

@@ -23,6 +23,8 @@ SEARCH_KNN, SEARCH_RADIUS, SEARCH_HYBRID = 0, 1, 2
 MAX_KNN = 64
 ICP_NSUMS = 32
 ICP_DESC_LEN = 24  # include/o3dx.h O3DX_ICP_DESC_LEN
+ICP_POINT_TO_PLANE, ICP_POINT_TO_POINT = 0, 1  # O3DX_ICP_POINT_TO_*
+ICP_ESTIMATIONS = {"point_to_plane": ICP_POINT_TO_PLANE, "point_to_point": ICP_POINT_TO_POINT}
 PCD_TYPES = {("F", 4): 1, ("F", 8): 2, ("U", 1): 3, ("U", 2): 4, ("U", 4): 5, ("I", 1): 6, ("I", 2): 7,
              ("I", 4): 8}
 PCD_RGB = 9
@@ -142,6 +144,20 @@ _SIGS = {
     "o3dx_dbscan": (_I32, [_P, _I64, _D, _I32, _P, _P, _P, _P, _SZ, _P]),
     "o3dx_dbscan_f64_workspace_bytes": (_SZ, [_I64]),
     "o3dx_dbscan_f64": (_I32, [_P, _I64, _D, _I32, _P, _P, _P, _P, _SZ, _P]),
+    # point-to-point ICP (additive to ABI 7)
+    "o3dx_icp_target_build_points": (_I32, [_P, _I64, _D, _P, _SZ, _P, _P]),
+    "o3dx_icp_accumulate_est": (_I32, [_P, _I64, _I32, _P, _P, _P, _D, _P, _P, _P, _P, _P, _I32, _P, _SZ, _P]),
+    "o3dx_icp_register_est": (_I32, [_P, _I64, _I32, _P, _P, _P, _I32, _D, _D, _D, _P, _P, _P, _P, _P, _P, _I32,
+                                     _I32, _P, _SZ, _P]),
+    "o3dx_registration_icp_est": (_I32, [_P, _I64, _P, _P, _I64, _D, _P, _I32, _D, _D, _P, _P, _P, _P, _P, _I32,
+                                         _I32, _P, _SZ, _P, _SZ, _P]),
+    "o3dx_icp_solve_point_to_point": (_I32, [_P, _I32, _P]),
+    "o3dx_icp_update_est": (_I32, [_P, _I32, _I32, _P]),
+    "o3dx_icp_target_build_points_f64": (_I32, [_P, _I64, _D, _P, _SZ, _P, _P]),
+    "o3dx_icp_register_est_f64": (_I32, [_P, _I64, _I32, _P, _P, _P, _I32, _D, _D, _D, _P, _P, _P, _P, _P, _P,
+                                         _I32, _I32, _P, _SZ, _P]),
+    "o3dx_registration_icp_est_f64": (_I32, [_P, _I64, _P, _P, _I64, _D, _P, _I32, _D, _D, _P, _P, _P, _P, _P,
+                                             _I32, _I32, _P, _SZ, _P, _SZ, _P]),
 }
 
 _lib = None

@@ -646,33 +646,54 @@ def plane_from_moments(sum_xyz, count, centred) -> np.ndarray:
     return out
 
 
-class ICPTarget:
-    """Persistent target structure (grid of target points + normals) for ICP."""
+def _estimation(estimation) -> int:
+    """The library's constant of an estimation name (ValueError on anything else)."""
+    try:
+        return N.ICP_ESTIMATIONS[estimation]
+    except (KeyError, TypeError):
+        raise ValueError(f"unknown ICP estimation {estimation!r}: one of {sorted(N.ICP_ESTIMATIONS)}") from None
 
-    def __init__(self, tgt: torch.Tensor, tgt_normals: torch.Tensor, max_correspondence_distance: float):
+
+class ICPTarget:
+    """Persistent target structure (grid of target points + normals) for ICP.
+    tgt_normals=None builds a target without normals, which serves the
+    point-to-point estimation only."""
+
+    def __init__(self, tgt: torch.Tensor, tgt_normals: Optional[torch.Tensor] = None,
+                 max_correspondence_distance: Optional[float] = None):
+        if max_correspondence_distance is None:
+            raise TypeError("ICPTarget: max_correspondence_distance is required")
         # float64 targets: a float64 grid (o3dx_icp_target_build_f64), float64 sources
         self.f64 = _is64(tgt)
         self.xyz = _xyz64(tgt, "target points") if self.f64 else _xyz(tgt, "target points")
-        self.normals = _xyz(tgt_normals.to(self.xyz.device), "target normals")
-        if self.normals.shape[0] != self.xyz.shape[0]:
+        self.normals = None if tgt_normals is None else _xyz(tgt_normals.to(self.xyz.device), "target normals")
+        if self.normals is not None and self.normals.shape[0] != self.xyz.shape[0]:
             raise RuntimeError("target normals must match target points")
         L = N.load()
         nt = self.xyz.shape[0]
         self.max_corr = float(max_correspondence_distance)
         wsb = L.o3dx_icp_target_f64_workspace_bytes if self.f64 else L.o3dx_icp_target_workspace_bytes
-        build = L.o3dx_icp_target_build_f64 if self.f64 else L.o3dx_icp_target_build
         self.ws = torch.empty(wsb(nt), dtype=torch.uint8, device=self.xyz.device)
         self.desc = np.zeros(N.ICP_DESC_LEN, np.float64)
-        N.check(build(N.ptr(self.xyz), N.ptr(self.normals), nt, self.max_corr, N.ptr(self.ws), self.ws.numel(),
-                      _np_ptr(self.desc), N.stream_ptr(self.xyz.device)), "icp_target_build")
+        tail = (nt, self.max_corr, N.ptr(self.ws), self.ws.numel(), _np_ptr(self.desc),
+                N.stream_ptr(self.xyz.device))
+        if self.normals is None:
+            build = L.o3dx_icp_target_build_points_f64 if self.f64 else L.o3dx_icp_target_build_points
+            N.check(build(N.ptr(self.xyz), *tail), "icp_target_build_points")
+        else:
+            build = L.o3dx_icp_target_build_f64 if self.f64 else L.o3dx_icp_target_build
+            N.check(build(N.ptr(self.xyz), N.ptr(self.normals), *tail), "icp_target_build")
 
     def accumulate(self, src: torch.Tensor, T: np.ndarray, want_corr: bool = False, absmax=None,
-                   return_fx: bool = False):
-        """Transform + 1-NN + point-to-plane moments: (sums[32], corr or None)
+                   return_fx: bool = False, estimation: str = "point_to_plane"):
+        """Transform + 1-NN + the estimation's moments: (sums[32], corr or None)
         (+ the (32, 4) int64 fx rows with return_fx).  `src` is (n,3) float32,
         or the (n,4) output of spatial_sort (faster).  absmax: |x|,|y|,|z|
         bounds of the WHOLE source (a sharded source passes the global ones);
-        default: spatial_sort's record of them, else the library measures src."""
+        default: spatial_sort's record of them, else the library measures src.
+        estimation "point_to_point": the anchored Umeyama moments
+        (include/o3dx.h), for icp_update(..., estimation="point_to_point")."""
+        est = _estimation(estimation)
         if self.f64:
             raise RuntimeError("ICPTarget.accumulate: float64 targets run the device loop (register)")
         sorted4 = src.ndim == 2 and src.shape[1] == 4
@@ -695,21 +716,24 @@ class ICPTarget:
         corr = torch.empty((max(ns, 1), 2), dtype=torch.int32, device=s.device) if want_corr else None
         nc = np.zeros(1, np.int64)
         ws = N.workspace(L.o3dx_icp_accumulate_workspace_bytes(ns), s.device, "icp_acc")
-        N.check(L.o3dx_icp_accumulate(N.ptr(s), ns, 1 if sorted4 else 0, N.ptr(self.ws), _np_ptr(self.desc),
-                                      _np_ptr(TT), self.max_corr, _np_ptr(am),
-                                      _np_ptr(sums), _np_ptr(fx), N.ptr(corr), _np_ptr(nc), N.ptr(ws), ws.numel(),
-                                      N.stream_ptr(s.device)), "icp_accumulate")
+        N.check(L.o3dx_icp_accumulate_est(N.ptr(s), ns, 1 if sorted4 else 0, N.ptr(self.ws), _np_ptr(self.desc),
+                                          _np_ptr(TT), self.max_corr, _np_ptr(am),
+                                          _np_ptr(sums), _np_ptr(fx), N.ptr(corr), _np_ptr(nc), est, N.ptr(ws),
+                                          ws.numel(), N.stream_ptr(s.device)), "icp_accumulate")
         out = (sums, (corr[: int(nc[0])] if want_corr else None))
         return out + (fx,) if return_fx else out
 
     def register(self, src: torch.Tensor, init=None, max_iteration: int = 30, relative_fitness: float = 1e-6,
-                 relative_rmse: float = 1e-6, absmax=None, want_corr: bool = False):
-        """Open3D registration_icp (point-to-plane) onto this target with the
-        whole loop on the device (o3dx_icp_register): each iteration's fused
-        correspondence + moments pass, the solve and the convergence test are
-        queued at once and the host waits once.  `src` as in accumulate (the
-        (n,4) spatial_sort output is faster).  -> dict(transformation,
-        fitness, inlier_rmse[, correspondence_set])."""
+                 relative_rmse: float = 1e-6, absmax=None, want_corr: bool = False,
+                 estimation: str = "point_to_plane", with_scaling: bool = False):
+        """Open3D registration_icp onto this target with the whole loop on the
+        device (o3dx_icp_register_est): each iteration's fused correspondence
+        + moments pass, the solve and the convergence test are queued at once
+        and the host waits once.  `src` as in accumulate (the (n,4)
+        spatial_sort output is faster).  estimation: "point_to_plane" or
+        "point_to_point" (Umeyama; with_scaling as Open3D's option).  ->
+        dict(transformation, fitness, inlier_rmse[, correspondence_set])."""
+        est = _estimation(estimation)
         sorted4 = src.ndim == 2 and src.shape[1] == 4
         if sorted4:
             N.require_device(src, "source points")
@@ -737,11 +761,11 @@ class ICPTarget:
         corr = torch.empty((max(ns, 1), 2), dtype=torch.int32, device=s.device) if want_corr else None
         nc = np.zeros(1, np.int64)
         ws = N.workspace(L.o3dx_icp_accumulate_workspace_bytes(ns), s.device, "icp_acc")
-        reg = L.o3dx_icp_register_f64 if self.f64 else L.o3dx_icp_register
+        reg = L.o3dx_icp_register_est_f64 if self.f64 else L.o3dx_icp_register_est
         N.check(reg(N.ptr(s), ns, 1 if sorted4 else 0, N.ptr(self.ws), _np_ptr(self.desc), _np_ptr(T0),
                     int(max_iteration), float(relative_fitness), float(relative_rmse), self.max_corr, _np_ptr(am),
-                    _np_ptr(T), _np_ptr(fit), _np_ptr(rm), N.ptr(corr), _np_ptr(nc), N.ptr(ws), ws.numel(),
-                    N.stream_ptr(s.device)), "icp_register")
+                    _np_ptr(T), _np_ptr(fit), _np_ptr(rm), N.ptr(corr), _np_ptr(nc), est, 1 if with_scaling else 0,
+                    N.ptr(ws), ws.numel(), N.stream_ptr(s.device)), "icp_register")
         out = {"transformation": T, "fitness": float(fit[0]), "inlier_rmse": float(rm[0])}
         if want_corr:
             out["correspondence_set"] = corr[: int(nc[0])]
@@ -843,13 +867,25 @@ def spatial_sort(xyz: torch.Tensor, target_occ: float = 8.0) -> torch.Tensor:
     return res
 
 
-def icp_update(sums, T: np.ndarray) -> np.ndarray:
-    """T <- solve(sums) * T in the library's own float64 order (o3dx_icp_update)."""
+def icp_update(sums, T: np.ndarray, estimation: str = "point_to_plane", with_scaling: bool = False) -> np.ndarray:
+    """T <- solve(sums) * T in the library's own float64 order (o3dx_icp_update_est)."""
+    est = _estimation(estimation)
     TT = np.array(T, np.float64).reshape(4, 4).copy()
-    rc = N.load().o3dx_icp_update(_np_ptr(_c(sums, np.float64)), _np_ptr(TT))
+    rc = N.load().o3dx_icp_update_est(_np_ptr(_c(sums, np.float64)), est, 1 if with_scaling else 0, _np_ptr(TT))
     if rc < 0:  # 1 solved, 0 singular (identity update, as Open3D), < 0 a library error
         N.check(rc, "icp_update")
     return TT
+
+
+def icp_solve_point_to_point(sums, with_scaling: bool = False, return_status: bool = False):
+    """The Umeyama update (4x4) of point-to-point sums (o3dx_icp_solve_point_to_point);
+    with return_status also 1 (solved) or 0 (the identity update)."""
+    upd = np.zeros((4, 4), np.float64)
+    rc = N.load().o3dx_icp_solve_point_to_point(_np_ptr(_c(sums, np.float64)), 1 if with_scaling else 0,
+                                                _np_ptr(upd))
+    if rc < 0:
+        N.check(rc, "icp_solve_point_to_point")
+    return (upd, rc) if return_status else upd
 
 
 def icp_solve(sums) -> np.ndarray:
@@ -860,16 +896,22 @@ def icp_solve(sums) -> np.ndarray:
     return upd
 
 
-def registration_icp(src: torch.Tensor, tgt: torch.Tensor, tgt_normals: torch.Tensor,
+def registration_icp(src: torch.Tensor, tgt: torch.Tensor, tgt_normals: Optional[torch.Tensor],
                      max_correspondence_distance: float, init=None, max_iteration: int = 30,
-                     relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, return_corr: bool = True):
-    """Open3D registration_icp + TransformationEstimationPointToPlane on one device.
-    A float64 source or target: both in float64 (o3dx_registration_icp_point_to_plane_f64)."""
+                     relative_fitness: float = 1e-6, relative_rmse: float = 1e-6, return_corr: bool = True,
+                     estimation: str = "point_to_plane", with_scaling: bool = False):
+    """Open3D registration_icp on one device with TransformationEstimationPointToPlane
+    (the default here) or, estimation="point_to_point", TransformationEstimationPointToPoint(with_scaling),
+    for which tgt_normals may be None.  A float64 source or target: both in
+    float64 (o3dx_registration_icp_est_f64)."""
+    est = _estimation(estimation)
+    if tgt_normals is None and est != N.ICP_POINT_TO_POINT:
+        raise RuntimeError("registration_icp: point-to-plane needs target normals")
     f64 = _is64(src) or _is64(tgt)
     cv = _xyz64 if f64 else _xyz
     s = cv(src, "source points")
     t = cv(tgt.to(s.device), "target points")
-    tn = _xyz(tgt_normals.to(s.device), "target normals")
+    tn = None if tgt_normals is None else _xyz(tgt_normals.to(s.device), "target normals")
     L = N.load()
     ns, nt = s.shape[0], t.shape[0]
     T0 = np.eye(4) if init is None else _c(init, np.float64).reshape(4, 4)
@@ -883,11 +925,11 @@ def registration_icp(src: torch.Tensor, tgt: torch.Tensor, tgt_normals: torch.Te
                       s.device, "icp_target")
     ws = N.workspace((L.o3dx_registration_icp_f64_workspace_bytes if f64 else
                       L.o3dx_registration_icp_workspace_bytes)(ns), s.device, "icp")
-    fn = L.o3dx_registration_icp_point_to_plane_f64 if f64 else L.o3dx_registration_icp_point_to_plane
+    fn = L.o3dx_registration_icp_est_f64 if f64 else L.o3dx_registration_icp_est
     rc = fn(N.ptr(s), ns, N.ptr(t), N.ptr(tn), nt, float(max_correspondence_distance), _np_ptr(T0),
             int(max_iteration), float(relative_fitness), float(relative_rmse), _np_ptr(T), _np_ptr(fit),
-            _np_ptr(rm), N.ptr(corr), _np_ptr(nc), N.ptr(tws), tws.numel(), N.ptr(ws), ws.numel(),
-            N.stream_ptr(s.device))
+            _np_ptr(rm), N.ptr(corr), _np_ptr(nc), est, 1 if with_scaling else 0, N.ptr(tws), tws.numel(),
+            N.ptr(ws), ws.numel(), N.stream_ptr(s.device))
     N.check(rc, "registration_icp")
     out = {"transformation": T, "fitness": float(fit[0]), "inlier_rmse": float(rm[0])}
     if return_corr:

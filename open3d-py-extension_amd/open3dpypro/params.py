@@ -35,6 +35,40 @@ class KDTreeSearchParamHybrid:
         return f"KDTreeSearchParamHybrid(radius={self.radius}, max_nn={self.max_nn})"
 
 
+class TransformationEstimationPointToPoint:
+    """Open3D's registration_icp default estimation (Umeyama; with_scaling
+    also estimates a uniform scale)."""
+
+    def __init__(self, with_scaling: bool = False):
+        self.with_scaling = bool(with_scaling)
+
+    def __repr__(self):
+        return f"TransformationEstimationPointToPoint(with_scaling={self.with_scaling})"
+
+
+class TransformationEstimationPointToPlane:
+    def __repr__(self):
+        return "TransformationEstimationPointToPlane()"
+
+
+def resolve_estimation(estimation, with_scaling: bool = False):
+    """-> (estimation name, with_scaling) of an estimation string or a
+    TransformationEstimation object (duck-typed on the class name and
+    .with_scaling, so genuine open3d.pipelines.registration objects work
+    too).  ValueError on anything else."""
+    if isinstance(estimation, str):
+        if estimation not in N.ICP_ESTIMATIONS:
+            raise ValueError(f"unknown ICP estimation {estimation!r}: one of {sorted(N.ICP_ESTIMATIONS)}")
+        return estimation, bool(with_scaling) and estimation == "point_to_point"
+    name = type(estimation).__name__
+    if name == "TransformationEstimationPointToPoint":
+        return "point_to_point", bool(getattr(estimation, "with_scaling", False))
+    if name == "TransformationEstimationPointToPlane":
+        return "point_to_plane", False
+    raise ValueError(f"unsupported ICP estimation {estimation!r}: 'point_to_plane', 'point_to_point' or a "
+                     "TransformationEstimationPointToPoint / TransformationEstimationPointToPlane object")
+
+
 def resolve(param):
     """-> (mode, knn, radius) for the C-ABI."""
     if param is None:

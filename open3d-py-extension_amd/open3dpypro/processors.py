@@ -373,21 +373,28 @@ class Processors:
             return res
 
     class ICP(PointCloudMatProcessor):
-        """Point-to-plane ICP of input 0 (source) onto input 1 (target, must
-        carry normals: ShapeType ...N).  Output: the transformed source;
-        meta[uuid] = {'transformation', 'fitness', 'inlier_rmse'}.  North-star
-        op — the reference has no ICP."""
+        """ICP of input 0 (source) onto input 1 (target).  estimation
+        "point_to_plane" (the default; the target must carry normals:
+        ShapeType ...N) or "point_to_point" (Umeyama, optionally with_scaling;
+        any target).  Output: the transformed source; meta[uuid] =
+        {'transformation', 'fitness', 'inlier_rmse'}.  North-star op — the
+        reference has no ICP."""
         title: str = "icp_point_to_plane"
         max_correspondence_distance: float = 0.02
         max_iteration: int = 30
         relative_fitness: float = 1e-6
         relative_rmse: float = 1e-6
         init: Optional[List[List[float]]] = None
+        estimation: str = "point_to_plane"
+        with_scaling: bool = False
         result: dict = {}
 
         def validate_pcd(self, pcd_idx, pcd):
-            if pcd_idx == 1 and not pcd.info.shape_type.contains_normals():
-                raise TypeError("ICP target must carry normals (ShapeType ending in 'N')")
+            if self.estimation not in ("point_to_plane", "point_to_point"):
+                raise ValueError(f"unknown ICP estimation {self.estimation!r}")
+            if (pcd_idx == 1 and self.estimation == "point_to_plane"
+                    and not pcd.info.shape_type.contains_normals()):
+                raise TypeError("point-to-plane ICP target must carry normals (ShapeType ending in 'N')")
 
         def build_out_mats(self, validated_pcds, converted_raw_pcds):
             self.out_mats = [PointCloudMat(shape_type=validated_pcds[0].info.shape_type).build(converted_raw_pcds[0])]
@@ -396,11 +403,12 @@ class Processors:
         def forward_raw(self, pcds_data, pcds_info=[], meta={}):
             src, tgt = pcds_data[0], pcds_data[1]
             st = pcds_info[1].shape_type
-            ncol = {ShapeType.XYZN: 3, ShapeType.XYZRGBN: 6, ShapeType.XYZiN: 4, ShapeType.XYZRGBiN: 7}[st]
-            tn = _to_gpu(tgt)[:, ncol:ncol + 3].float().contiguous()
+            ncol = {ShapeType.XYZN: 3, ShapeType.XYZRGBN: 6, ShapeType.XYZiN: 4, ShapeType.XYZRGBiN: 7}.get(st)
+            tn = None if ncol is None else _to_gpu(tgt)[:, ncol:ncol + 3].float().contiguous()
             r = ops.registration_icp(_xyz(src), _xyz(tgt), tn, self.max_correspondence_distance, self.init,
                                      self.max_iteration, self.relative_fitness, self.relative_rmse,
-                                     return_corr=False)
+                                     return_corr=False, estimation=self.estimation,
+                                     with_scaling=self.with_scaling)
             T = r["transformation"]
             self.result = {"transformation": T.tolist(), "fitness": r["fitness"], "inlier_rmse": r["inlier_rmse"]}
             meta[self.uuid] = self.result
