@@ -851,6 +851,71 @@ size_t o3dx_dbscan_f64_workspace_bytes(int64_t n);
 int o3dx_dbscan_f64(const double* xyz_dev, int64_t n, double eps, int min_samples, int32_t* labels_dev,
                     uint8_t* core_dev, int64_t* n_clusters_host, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------- floor-map segmentation
+ * Rasterisation, image labelling and grouping behind the reference's
+ * to_2D_Img (PointCloud.py:785-823), simple_seg_connected_components and
+ * simple_seg_connected_components_by_img (PointCloud.py:888-916) and
+ * Processors.SimpleSegConnectedComponents (processors.py:772-799); additive to
+ * ABI 7.
+ *
+ * Rasterisation.  bounds_host = {minx, miny, maxx, maxy} of the cloud's x and
+ * y (float64; float32 points upcast exactly).  With ir = 1 / resolution,
+ * tx = ir * (-minx), ty = ir * (-miny), every operation rounded to float64 on
+ * its own (no fused multiply-add):
+ *     ix = (int) rint(x * ir + tx),   iy = (int) rint(y * ir + ty)
+ * (rint: round half to even, numpy's round).  The image is h rows of w pixels,
+ * w = rint(maxx * ir + tx), h = rint(maxy * ir + ty): the largest ix / iy of
+ * the cloud, both maps being monotone.  ix is then clamped to [0, w - 1] and
+ * iy to [0, h - 1] — the last column and row fold into the one before, as in
+ * the reference.  o3dx_raster2d_size (host only) returns {w, h} in wh_host;
+ * either may be 0 (every point in one pixel column or row: the reference's
+ * indexing raises there, and o3dx_raster2d returns EINVAL).  o3dx_raster2d /
+ * o3dx_raster2d_f64 write pix_dev (n x 2 int32, {ix, iy}), clear img_dev
+ * (h x w uint8, img_cap >= w * h pixels) and store 255 on every hit pixel;
+ * winner_dev (h x w int32, nullable) receives the highest point index on each
+ * pixel, -1 on an empty one (numpy's fancy assignment lets the last write
+ * win: the colour image is built from it on the host).  Enqueue only; the
+ * coordinates must be finite (a NaN lands on pixel 0, never outside).
+ * Errors, before any device call: EINVAL for a resolution <= 0 or not finite,
+ * null or non-finite bounds, max < min, n outside [1, 2^31), a null pointer, an
+ * empty image; ENOTSUP for w * h >= 2^31; ENOMEM for img_cap < w * h.
+ *
+ * Connected components.  Foreground: a non-zero pixel; connectivity 8; label
+ * 0 is the background; the components are numbered 1, 2, ... in ascending
+ * row-major position of their first pixel (the smallest y * w + x; this is
+ * also scipy.ndimage.label's numbering.  cv2 numbers by first 2 x 2 block
+ * instead; the numbering is observable only through ties of equal area).
+ * labels_dev: h x w int32.  areas_dev: int64, o3dx_ccl2d_max_labels(w, h) + 1
+ * = ceil(w / 2) * ceil(h / 2) + 1 entries, of which [0, *n_labels_host] are
+ * written: areas[l] = pixel count of label l, areas[0] = the zero pixels.
+ * Tile-local labelling in LDS, a global union-find on the tile seams only;
+ * integer atomics, the result does not depend on launch order.  Synchronises.
+ * Errors, before any device call: EINVAL for w < 1, h < 1 or a null pointer;
+ * ENOTSUP for w * h >= 2^31; ENOMEM for a workspace below
+ * o3dx_ccl2d_workspace_bytes(w, h) (0 outside the range).
+ *
+ * Grouping.  point_label_dev[i] = labels_dev[iy_i * w + ix_i] for pix_dev
+ * (n x 2 int32); order_dev (n int32): the point indices grouped by label,
+ * ascending inside each label (a stable radix sort of ceil(log2(n_labels + 1))
+ * bits); counts_dev (int64, n_labels + 1): points per label.  Synchronises.
+ * EINVAL (after the device pass) if a pixel lies outside the image or a label
+ * outside [0, n_labels]; before any device call EINVAL for n outside
+ * [1, 2^31), a bad image size or a null pointer, ENOMEM for a workspace below
+ * o3dx_label_group_workspace_bytes(n, n_labels). */
+int o3dx_raster2d_size(double resolution, const double* bounds_host, int64_t* wh_host);
+int o3dx_raster2d(const float* xyz_dev, int64_t n, double resolution, const double* bounds_host, int32_t* pix_dev,
+                  uint8_t* img_dev, int32_t* winner_dev, int64_t img_cap, void* stream);
+int o3dx_raster2d_f64(const double* xyz_dev, int64_t n, double resolution, const double* bounds_host,
+                      int32_t* pix_dev, uint8_t* img_dev, int32_t* winner_dev, int64_t img_cap, void* stream);
+size_t o3dx_ccl2d_workspace_bytes(int64_t w, int64_t h);
+int64_t o3dx_ccl2d_max_labels(int64_t w, int64_t h);
+int o3dx_ccl2d(const uint8_t* img_dev, int64_t w, int64_t h, int32_t* labels_dev, int64_t* areas_dev,
+               int64_t* n_labels_host, void* ws, size_t ws_bytes, void* stream);
+size_t o3dx_label_group_workspace_bytes(int64_t n, int64_t n_labels);
+int o3dx_label_group(const int32_t* pix_dev, int64_t n, const int32_t* labels_dev, int64_t w, int64_t h,
+                     int64_t n_labels, int32_t* point_label_dev, int32_t* order_dev, int64_t* counts_dev, void* ws,
+                     size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

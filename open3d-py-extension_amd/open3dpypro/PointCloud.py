@@ -16,9 +16,12 @@ the reference.
 The hot-path methods call libo3dx.so (ops.py); there is no CPU fallback —
 without an MI355X they raise RuntimeError.  Host-only helpers (selections by
 numpy predicate, splitting, I/O) run anywhere.  DBSCAN (the reference's
-sklearn call) runs on the GPU and returns sklearn's labels (ops.dbscan).  Out
-of scope and not mirrored: to_2D_Img, the
-colour-cosine selections.
+sklearn call) runs on the GPU and returns sklearn's labels (ops.dbscan).
+to_2D_Img and the floor-map segmentation (simple_seg_connected_components,
+simple_seg_connected_components_by_img; the reference's cv2 labelling) run on
+the GPU too: ops.raster2d / ccl2d / label_group.  Out of scope (SURVEY.md §2
+row 5) and not mirrored: the colour-cosine selections, and the reference's
+other cv2 methods (detect_3d_circles, read_single_RGB).
 """
 from __future__ import annotations
 
@@ -929,6 +932,128 @@ class PointCloud(PointCloudUtility):
         ends = np.cumsum(counts)  # label -1 first
         pcds = [self._select_by_idx(order[ends[i]:ends[i + 1]]) for i in range(k)]
         return pcds, lab.cpu().numpy().astype(np.int64)
+
+    # ------------------------------------------------ floor-map segmentation
+    def _finite_points(self) -> bool:
+        if self._pts_host is not None:
+            return bool(np.isfinite(self._pts_host).all())
+        src = self._pts64 if self._pts64 is not None else self._pts
+        return bool(torch.isfinite(src).all().item())
+
+    def _raster(self, resolution: float, want_winner: bool = False):
+        """ops.raster2d of this cloud's get_points() values (the float64 host
+        values when the cloud holds them, else the float32 points)."""
+        resolution = float(resolution)
+        if not (resolution > 0.0) or not np.isfinite(resolution):
+            raise ValueError(f"resolution must be a finite float > 0, got {resolution}")
+        if not self.has_points():
+            raise ValueError("to_2D_Img: the cloud has no points")
+        if not self._finite_points():
+            raise ValueError("to_2D_Img: the coordinates must be finite")
+        return ops.raster2d(self._plane_points(), resolution, want_winner=want_winner)
+
+    def to_2D_Img(self, resolution: float = 0.05, color: bool = False):
+        """The cloud's (x, y) rasterised at `resolution` on the GPU (reference
+        PointCloud.py:785-823; include/o3dx.h states the rule) ->
+        (img, minx, T, miny, invT, resolution, idx2img).  img: (sizey, sizex)
+        uint8, 255 on every hit pixel; with color=True and colours present
+        (sizey, sizex, 3) uint8, the colour (get_colors() * 255 as uint8) of
+        the highest point index on each pixel (numpy's last write wins).  T
+        maps the points to pixel coordinates, invT = inv(T).  idx2img is an
+        (N,2) int64 numpy array of (ix, iy) where the reference returns a
+        Python list of N tuples: every consumer does np.asarray(idx2img), for
+        which the array is identical.  ValueError for a resolution <= 0 or not
+        finite, an empty cloud or non-finite coordinates (the reference's
+        result there is garbage); IndexError when all points fall in one pixel
+        column or row, as the reference's indexing raises."""
+        usecolor = bool(color) and self.has_colors()
+        if color and not usecolor:
+            print('has no rgb data, cannot use color!')
+        r = self._raster(resolution, want_winner=usecolor)
+        minx, miny = r["minx"], r["miny"]
+        T = np.asarray([[1., 0., 0., -minx],
+                        [0., 1., 0., -miny],
+                        [0., 0., 1., 0.],
+                        [0., 0., 0., 1.]])
+        ir = 1 / resolution
+        T = np.asarray([[ir, 0., 0., 0.],
+                        [0., ir, 0., 0.],
+                        [0., 0., ir, 0.],
+                        [0., 0., 0., 1.]]) @ T
+        if usecolor:
+            win = r["winner"].cpu().numpy()
+            rgb = (self.get_colors() * 255).astype(np.uint8)
+            img = np.zeros((r["h"], r["w"], 3), np.uint8)
+            hit = win >= 0
+            img[hit] = rgb[win[hit]]
+        else:
+            img = r["img"].cpu().numpy()
+        idx2img = r["pix"].cpu().numpy().astype(np.int64)
+        return img, minx, T, miny, np.linalg.inv(T), resolution, idx2img
+
+    @staticmethod
+    def _ccl_ranking(areas: np.ndarray) -> np.ndarray:
+        """The labels the segmentation returns, in order: all labels (the
+        background included) ranked by area, descending — equal areas with the
+        higher label first (this project's rule; the reference's unstable
+        argsort leaves ties open) — without the first of that ranking,
+        whichever label it is (reference PointCloud.py:894, 910)."""
+        return np.argsort(np.asarray(areas), kind="stable")[::-1][1:]
+
+    def _ccl_clouds(self, img_dev: torch.Tensor, pix_dev: torch.Tensor, top_n=None, minpoints: int = 0):
+        labels, areas, k = ops.ccl2d(img_dev)
+        _, order, counts = ops.label_group(pix_dev, labels, k)
+        counts = counts.cpu().numpy()
+        ends = np.concatenate([[0], np.cumsum(counts)])
+        rank = self._ccl_ranking(areas.cpu().numpy())
+        if top_n is not None:
+            rank = rank[:max(int(top_n), 0)]
+        pcds = []
+        for l in rank:
+            if counts[l] < minpoints:
+                continue
+            pcds.append(self._select_by_idx(order[ends[l]:ends[l + 1]]))
+        return pcds
+
+    def simple_seg_connected_components_by_img(self, img: np.ndarray, minx=None, T=None, miny=None, invT=None,
+                                               resolution=None, idx2img=None):
+        """One cloud per 8-connected component of the 2-D uint8 image `img`
+        (non-zero = foreground), labelled on the GPU: the points whose pixel
+        idx2img[i] = (ix, iy) carries the component's label, for every label of
+        _ccl_ranking (no top_n, no minpoints: empty clouds are included)
+        (reference PointCloud.py:888-897; the arguments are to_2D_Img's
+        tuple).  IndexError when len(idx2img) != size() or an index lies
+        outside the image — a negative one too, where numpy would wrap."""
+        im = _as_np(img)
+        if im.ndim != 2:
+            raise ValueError(f"img must be a 2-D image, got shape {im.shape}")
+        if im.dtype != np.uint8:
+            im = (im != 0).astype(np.uint8)
+        idx = np.asarray(idx2img)
+        if idx.ndim != 2 or idx.shape[1] != 2 or len(idx) != self.size():
+            raise IndexError(f"idx2img must hold one (ix, iy) per point: shape {idx.shape} for {self.size()} points")
+        if len(idx) == 0 or im.size == 0:
+            raise IndexError("simple_seg_connected_components_by_img: no points or an empty image")
+        h, w = im.shape
+        if idx.min() < 0 or idx[:, 0].max() >= w or idx[:, 1].max() >= h:
+            raise IndexError(f"idx2img has an index outside the {h} x {w} image")
+        dev = N.default_device()
+        img_dev = torch.as_tensor(np.ascontiguousarray(im), device=dev)
+        pix_dev = torch.as_tensor(np.ascontiguousarray(idx, dtype=np.int32), device=dev)
+        return self._ccl_clouds(img_dev, pix_dev)
+
+    def simple_seg_connected_components(self, plane, thickness: float = 0.05, resolution: float = 0.1,
+                                        minpoints: int = 20, top_n: int = 100):
+        """The reference's floor-map segmentation (PointCloud.py:899-916) on
+        the GPU: the slab within `thickness` of `plane`, rasterised at
+        `resolution`, its 8-connected blobs labelled; the next top_n labels of
+        _ccl_ranking each give the slab's points on that blob (ascending, all
+        attributes carried), skipped below minpoints.  [] for an empty slab."""
+        slab = self._select_by_idx(self._plane_index_dev(plane, thickness))
+        if slab.size() == 0:
+            return []
+        r = slab._raster(resolution)
+        return slab._ccl_clouds(r["img"], r["pix"], top_n=top_n, minpoints=minpoints)
 
     def registration_icp(self, target: "PointCloudBase", max_correspondence_distance: float, init=None,
                          max_iteration: int = 30, relative_fitness: float = 1e-6, relative_rmse: float = 1e-6,

@@ -158,6 +158,15 @@ _SIGS = {
                                          _I32, _I32, _P, _SZ, _P]),
     "o3dx_registration_icp_est_f64": (_I32, [_P, _I64, _P, _P, _I64, _D, _P, _I32, _D, _D, _P, _P, _P, _P, _P,
                                              _I32, _I32, _P, _SZ, _P, _SZ, _P]),
+    # floor-map segmentation: rasterisation, image labelling, grouping (additive to ABI 7)
+    "o3dx_raster2d_size": (_I32, [_D, _P, _P]),
+    "o3dx_raster2d": (_I32, [_P, _I64, _D, _P, _P, _P, _P, _I64, _P]),
+    "o3dx_raster2d_f64": (_I32, [_P, _I64, _D, _P, _P, _P, _P, _I64, _P]),
+    "o3dx_ccl2d_workspace_bytes": (_SZ, [_I64, _I64]),
+    "o3dx_ccl2d_max_labels": (_I64, [_I64, _I64]),
+    "o3dx_ccl2d": (_I32, [_P, _I64, _I64, _P, _P, _P, _P, _SZ, _P]),
+    "o3dx_label_group_workspace_bytes": (_SZ, [_I64, _I64]),
+    "o3dx_label_group": (_I32, [_P, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _SZ, _P]),
 }
 
 _lib = None

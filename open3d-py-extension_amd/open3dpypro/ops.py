@@ -406,6 +406,99 @@ def dbscan(xyz: torch.Tensor, eps: float, min_samples: int, return_core: bool = 
     return labels, int(cnt[0])
 
 
+def raster2d_size(resolution: float, minx: float, miny: float, maxx: float, maxy: float):
+    """(w, h) of the reference's to_2D_Img image for these x / y bounds
+    (o3dx_raster2d_size, host only; either may be 0)."""
+    wh = np.zeros(2, np.int64)
+    b = _c([minx, miny, maxx, maxy], np.float64)
+    N.check(N.load().o3dx_raster2d_size(float(resolution), _np_ptr(b), _np_ptr(wh)), "raster2d_size")
+    return int(wh[0]), int(wh[1])
+
+
+def raster2d(xyz: torch.Tensor, resolution: float, want_winner: bool = False):
+    """The reference's to_2D_Img rasterisation (PointCloud.py:785-823) on the
+    device (o3dx_raster2d / o3dx_raster2d_f64 by the points' dtype;
+    include/o3dx.h states the rule).  Returns a dict of device tensors and
+    host scalars: pix (n,2) int32 {ix, iy}, img (h,w) uint8 (255 on a hit
+    pixel), winner (h,w) int32 (the highest point index per pixel, -1 when
+    empty; None unless want_winner), minx, miny (float64), w, h.
+    ValueError for a resolution <= 0 or not finite and for an empty cloud;
+    IndexError when the image would have no column or no row (all points in
+    one pixel column or row), as the reference's indexing raises."""
+    resolution = float(resolution)
+    if not (resolution > 0.0) or not np.isfinite(resolution):
+        raise ValueError(f"resolution must be a finite float > 0, got {resolution}")
+    if isinstance(xyz, torch.Tensor) and xyz.ndim == 2 and xyz.shape[0] == 0:
+        raise ValueError("raster2d: found a cloud with 0 points (a minimum of 1 is required)")
+    f64 = _is64(xyz)
+    x = _xyz64(xyz) if f64 else _xyz(xyz)
+    mn, mx = aabb(x)
+    if not (np.isfinite(mn).all() and np.isfinite(mx).all()):
+        raise ValueError("raster2d: the coordinates must be finite")
+    L = N.load()
+    n = x.shape[0]
+    dev = x.device
+    w, h = raster2d_size(resolution, mn[0], mn[1], mx[0], mx[1])
+    if w < 1 or h < 1:
+        raise IndexError(f"raster2d: the image would be {h} x {w} (all points in one pixel row or column)")
+    b = _c([mn[0], mn[1], mx[0], mx[1]], np.float64)
+    pix = torch.empty((n, 2), dtype=torch.int32, device=dev)
+    img = torch.empty((h, w), dtype=torch.uint8, device=dev)
+    winner = torch.empty((h, w), dtype=torch.int32, device=dev) if want_winner else None
+    fn = L.o3dx_raster2d_f64 if f64 else L.o3dx_raster2d
+    N.check(fn(N.ptr(x), n, resolution, _np_ptr(b), N.ptr(pix), N.ptr(img), N.ptr(winner), w * h,
+               N.stream_ptr(dev)), "raster2d")
+    return {"pix": pix, "img": img, "winner": winner, "minx": np.float64(mn[0]), "miny": np.float64(mn[1]),
+            "w": w, "h": h}
+
+
+def ccl2d(img: torch.Tensor):
+    """8-connected components of a 2-D uint8 device image (o3dx_ccl2d): a
+    non-zero pixel is foreground, label 0 the background, components numbered
+    1, 2, ... by ascending row-major position of their first pixel.  Returns
+    (labels (h,w) int32, areas (k+1,) int64 — areas[0] the zero pixels —, k),
+    the first two on the device."""
+    N.require_device(img, "img")
+    if img.ndim != 2 or img.dtype != torch.uint8:
+        raise RuntimeError(f"img must be a 2-D uint8 tensor, got {tuple(img.shape)} {img.dtype}")
+    im = img.contiguous()
+    L = N.load()
+    h, w = int(im.shape[0]), int(im.shape[1])
+    dev = im.device
+    labels = torch.empty((h, w), dtype=torch.int32, device=dev)
+    areas = torch.empty(int(L.o3dx_ccl2d_max_labels(w, h)) + 1, dtype=torch.int64, device=dev)
+    k = np.zeros(1, np.int64)
+    ws = N.workspace(int(L.o3dx_ccl2d_workspace_bytes(w, h)), dev)
+    N.check(L.o3dx_ccl2d(N.ptr(im), w, h, N.ptr(labels), N.ptr(areas), _np_ptr(k), N.ptr(ws), ws.numel(),
+                         N.stream_ptr(dev)), "ccl2d")
+    return labels, areas[: int(k[0]) + 1], int(k[0])
+
+
+def label_group(pix: torch.Tensor, labels: torch.Tensor, k: int):
+    """The points grouped by the label of their pixel (o3dx_label_group): pix
+    (n,2) int32 {ix, iy}, labels (h,w) int32 with values in [0, k].  Returns
+    device tensors (point_label (n,) int32, order (n,) int32 — the point
+    indices grouped by label, ascending inside each —, counts (k+1,) int64).
+    RuntimeError (EINVAL) when a pixel lies outside the image."""
+    N.require_device(pix, "pix")
+    N.require_device(labels, "labels")
+    if pix.ndim != 2 or pix.shape[1] != 2 or labels.ndim != 2:
+        raise RuntimeError(f"pix must be (n,2) and labels (h,w), got {tuple(pix.shape)} and {tuple(labels.shape)}")
+    px = pix.to(torch.int32).contiguous()
+    lb = labels.to(torch.int32).contiguous()
+    L = N.load()
+    n = int(px.shape[0])
+    h, w = int(lb.shape[0]), int(lb.shape[1])
+    dev = px.device
+    point_label = torch.empty(n, dtype=torch.int32, device=dev)
+    order = torch.empty(n, dtype=torch.int32, device=dev)
+    counts = torch.empty(int(k) + 1, dtype=torch.int64, device=dev)
+    ws = N.workspace(int(L.o3dx_label_group_workspace_bytes(n, int(k))), dev)
+    N.check(L.o3dx_label_group(N.ptr(px), n, N.ptr(lb), w, h, int(k), N.ptr(point_label), N.ptr(order),
+                               N.ptr(counts), N.ptr(ws), ws.numel(), N.stream_ptr(dev)), "label_group")
+    return point_label, order, counts
+
+
 def ransac_samples(n: int, ransac_n: int, num_iterations: int, seed: int) -> np.ndarray:
     """Open3D RandomSampler over mt19937(seed): (iters, ransac_n) int32."""
     out = np.empty((max(num_iterations, 1), ransac_n), np.int32)

@@ -441,6 +441,33 @@ class Processors:
                 raise NotImplementedError("forward_raw function is not set")
             return self._forward_raw(pcds_data, pcds_info, meta)
 
+    class SimpleSegConnectedComponents(PointCloudMatProcessor):
+        """PointCloud.simple_seg_connected_components of each numpy mat's xyz
+        (reference processors.py:772-799): the blobs' points, padded with
+        empty (0,3) arrays up to top_n entries; the out mats are XYZ."""
+        title: str = "simple_seg_connected_components"
+        plane: List[float] = [0, 0, 1.0, 0.0]
+        thickness: float = 0.05
+        resolution: float = 0.1
+        minpoints: int = 20
+        top_n: int = 100
+
+        def build_out_mats(self, validated_pcds, converted_raw_pcds):
+            self.out_mats = [PointCloudMat(shape_type=ShapeType.XYZ).build(pcd) for pcd in converted_raw_pcds]
+            return self.out_mats
+
+        def validate_pcd(self, pcd_idx, pcd: PointCloudMat):
+            pcd.require_ndarray()
+
+        def forward_raw(self, pcds_data, pcds_info=[], meta={}):
+            res = []
+            for pcd in pcds_data:
+                tmp = PointCloud(pcd[:, :3]).simple_seg_connected_components(
+                    np.asarray(self.plane), self.thickness, self.resolution, self.minpoints, self.top_n)
+                res += [c.get_points() for c in tmp]
+            res += [np.zeros((0, 3)) for _ in range(self.top_n - len(res))]
+            return res
+
 
 class PointCloudMatProcessors:
     """Pipeline runner (reference processors.py:1043-1098)."""
