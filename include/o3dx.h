@@ -916,6 +916,53 @@ int o3dx_label_group(const int32_t* pix_dev, int64_t n, const int32_t* labels_de
                      int64_t n_labels, int32_t* point_label_dev, int32_t* order_dev, int64_t* counts_dev, void* ws,
                      size_t ws_bytes, void* stream);
 
+/* --------------------------- spanning trees and consistent normal orientation
+ * Open3D 0.19 OrientNormalsConsistentTangentPlane(k) (reference
+ * PointCloud.py:69-70, estimate_normals(method="poisson")); additive to ABI 7.
+ * Every edge comparison uses one strict total order on undirected edges,
+ * (w, min(i,j), max(i,j)), so both trees are unique — duplicate points and
+ * lattices included — and the result does not depend on launch order.
+ *
+ * o3dx_emst: the Euclidean minimum spanning tree of the n points, the MST of
+ * the complete graph under w = d^2(i,j) = ((dx dx) + dy dy) + dz dz in float64
+ * on the float32 coordinates upcast exactly.  Open3D finds the same tree
+ * inside the Delaunay edges; here it is Boruvka rounds over the search grid,
+ * so fewer than 4 points or coplanar points simply work.  edges_out_dev:
+ * (n - 1, 2) int32 rows {lo, hi}, lo < hi, sorted by (lo, hi).  knn_idx_dev /
+ * k: the points' neighbour lists when the caller has them (nullable, k >= 0;
+ * a hint only, unused at present).
+ *
+ * o3dx_orient_normals_tangent_plane, given each point's neighbour list
+ * knn_idx_dev ((n, k) int32, o3dx_knn_search's rows on the cloud itself with
+ * knn = min(k, n); entries < 0 and the point itself are skipped):
+ *   1. the Riemannian graph = the arcs {i, knn[i][*]} united with the EMST;
+ *   2. its MST under w = 1.0 - |dot|, dot = ((nx nx') + ny ny') + nz nz' in
+ *      float64 on the float32 normals, no fused multiply-add;
+ *   3. the root is the lowest index among the points of maximal z, flipped
+ *      iff its nz < 0; along the tree a child is flipped iff
+ *      dot(parent as oriented, child) < 0 (dot == 0 never flips), i.e.
+ *      flip[i] = flip[root] ^ (the number of tree edges with dot < 0 on the
+ *      path root -> i, mod 2);
+ *   4. a flipped normal has its three sign bits toggled in normals_inout_dev;
+ *      magnitudes stay bit-identical.
+ * tree_out_dev (nullable): the (n - 1, 2) tree edges as o3dx_emst writes them;
+ * flipped_out_dev (nullable): n bytes, 1 = flipped.  Open3D 0.18+'s lambda /
+ * cos_alpha_tol arguments are not offered (their defaults are inert).
+ * Coordinates and normals must be finite.
+ * Errors, before any device call: EINVAL for n outside [1, 2^31), k < 0
+ * (o3dx_emst) or k < 1, a null xyz / edges (n > 1) / knn_idx / normals; ENOMEM
+ * for a workspace below o3dx_*_workspace_bytes (0 for arguments outside the
+ * range).  EIO for a HIP error, a raised iteration bound, or a tree that does
+ * not reach n - 1 edges (non-finite input).  At most ceil(log2 n) rounds per
+ * tree, one small host read per round.  Synchronises the stream. */
+size_t o3dx_emst_workspace_bytes(int64_t n);
+int o3dx_emst(const float* xyz_dev, int64_t n, const int32_t* knn_idx_dev, int k, int32_t* edges_out_dev, void* ws,
+              size_t ws_bytes, void* stream);
+size_t o3dx_orient_normals_workspace_bytes(int64_t n, int k);
+int o3dx_orient_normals_tangent_plane(const float* xyz_dev, int64_t n, const int32_t* knn_idx_dev, int k,
+                                      float* normals_inout_dev, int32_t* tree_out_dev, uint8_t* flipped_out_dev,
+                                      void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

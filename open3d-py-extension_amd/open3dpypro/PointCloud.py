@@ -19,7 +19,10 @@ numpy predicate, splitting, I/O) run anywhere.  DBSCAN (the reference's
 sklearn call) runs on the GPU and returns sklearn's labels (ops.dbscan).
 to_2D_Img and the floor-map segmentation (simple_seg_connected_components,
 simple_seg_connected_components_by_img; the reference's cv2 labelling) run on
-the GPU too: ops.raster2d / ccl2d / label_group.  Out of scope (SURVEY.md §2
+the GPU too: ops.raster2d / ccl2d / label_group.  estimate_normals(method=
+"poisson") orients the stored normals on the GPU (Open3D's
+orient_normals_consistent_tangent_plane: ops.orient_normals_tangent_plane).
+Out of scope (SURVEY.md §2
 row 5) and not mirrored: the colour-cosine selections, and the reference's
 other cv2 methods (detect_3d_circles, read_single_RGB).
 """
@@ -329,13 +332,80 @@ class PointCloudBase:
     def estimate_normals(self, method="default", param=KDTreeSearchParamKNN(30)):
         """Open3D EstimateNormals(param, fast_normal_computation=True) on the GPU
         (reference PointCloud.py:68-73).  Existing normals orient the result."""
-        if method == "poisson":
-            raise NotImplementedError("orient_normals_consistent_tangent_plane is outside the GPU hot path")
+        if method == "poisson":  # reference PointCloud.py:69-70
+            return self.orient_normals_consistent_tangent_plane(k=30)
         mode, knn, radius = resolve(param)
         x = self._hot_points()
         prior = self._normals if self.has_normals() else None
         self._normals = ops.estimate_normals(x, mode=mode, knn=knn, radius=radius, prior=prior,
                                              voxel_grid=None if self._wide else self._kept_voxel_grid(x))
+        return self
+
+    def orient_normals_consistent_tangent_plane(self, k: int = 30):
+        """Open3D OrientNormalsConsistentTangentPlane(k) on the GPU
+        (ops.orient_normals_tangent_plane; include/o3dx.h states the rule):
+        the stored normals keep their magnitudes and get consistent signs
+        along the minimum spanning tree of the Riemannian graph (k nearest
+        neighbours united with the Euclidean MST), rooted at the highest
+        point.  Returns self.  An empty cloud is left as it is; RuntimeError,
+        as Open3D, for a cloud without normals; ValueError for k < 1 or
+        non-finite coordinates, all before any GPU work.  Fewer than 4 or coplanar points work (Open3D's
+        Qhull step fails there); Open3D 0.18+'s lambda / cos_alpha_tol are
+        not offered.  float64 clouds that float32 cannot hold raise
+        NotImplementedError."""
+        if not self.has_points():
+            return self
+        if not self.has_normals():
+            raise RuntimeError("No normals in the PointCloud. Call EstimateNormals() first.")
+        if int(k) != k or int(k) < 1:
+            raise ValueError(f"k must be an int >= 1, got {k}")
+        if self._wide:
+            raise NotImplementedError("orient_normals_consistent_tangent_plane: float64 clouds that float32 cannot "
+                                      "hold are outside this implementation (pass float32 values)")
+        if not self._finite_points():
+            raise ValueError("orient_normals_consistent_tangent_plane: the coordinates must be finite")
+        self._normals = ops.orient_normals_tangent_plane(self._dev_points(), self._normals, int(k))
+        return self
+
+    def _exact_points_like(self, t: torch.Tensor) -> torch.Tensor:
+        """get_points()'s float64 values as a tensor on t's device."""
+        if self._pts_host is not None:
+            return torch.as_tensor(self._pts_host, dtype=torch.float64, device=t.device)
+        if self._pts64 is not None:
+            return self._pts64.to(t.device)
+        return self._pts.to(t.device).double()
+
+    def orient_normals_to_align_with_direction(self, orientation_reference=(0.0, 0.0, 1.0)):
+        """Open3D OrientNormalsToAlignWithDirection: a zero normal becomes the
+        reference, any other is negated iff n . ref < 0.  Returns self."""
+        if not self.has_normals():
+            raise RuntimeError("No normals in the PointCloud. Call EstimateNormals() first.")
+        n = self._normals
+        ref = torch.as_tensor(np.asarray(orientation_reference, np.float64).reshape(3), device=n.device)
+        nd = n.double()
+        zero = (nd == 0).all(dim=1, keepdim=True)
+        flip = ((nd * ref).sum(dim=1, keepdim=True) < 0)
+        out = torch.where(flip, -n, n)
+        self._normals = torch.where(zero, ref.float().expand_as(n), out).contiguous()
+        return self
+
+    def orient_normals_towards_camera_location(self, camera_location=(0.0, 0.0, 0.0)):
+        """Open3D OrientNormalsTowardsCameraLocation, ref = camera - point: a
+        zero normal becomes ref normalised ((0, 0, 1) when ref is zero too), any
+        other is negated iff n . ref < 0.  Returns self."""
+        if not self.has_normals():
+            raise RuntimeError("No normals in the PointCloud. Call EstimateNormals() first.")
+        n = self._normals
+        cam = torch.as_tensor(np.asarray(camera_location, np.float64).reshape(3), device=n.device)
+        ref = cam - self._exact_points_like(n)
+        nd = n.double()
+        zero = (nd == 0).all(dim=1, keepdim=True)
+        flip = ((nd * ref).sum(dim=1, keepdim=True) < 0)
+        out = torch.where(flip, -n, n)
+        norm = ref.norm(dim=1, keepdim=True)
+        up = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float64, device=n.device).expand_as(ref)
+        fill = torch.where(norm == 0, up, ref / torch.where(norm == 0, torch.ones_like(norm), norm))
+        self._normals = torch.where(zero, fill.float(), out).contiguous()
         return self
 
     def _kept_voxel_grid(self, x):

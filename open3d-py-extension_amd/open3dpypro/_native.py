@@ -167,6 +167,11 @@ _SIGS = {
     "o3dx_ccl2d": (_I32, [_P, _I64, _I64, _P, _P, _P, _P, _SZ, _P]),
     "o3dx_label_group_workspace_bytes": (_SZ, [_I64, _I64]),
     "o3dx_label_group": (_I32, [_P, _I64, _P, _I64, _I64, _I64, _P, _P, _P, _P, _SZ, _P]),
+    # spanning trees and consistent normal orientation (additive to ABI 7)
+    "o3dx_emst_workspace_bytes": (_SZ, [_I64]),
+    "o3dx_emst": (_I32, [_P, _I64, _P, _I32, _P, _P, _SZ, _P]),
+    "o3dx_orient_normals_workspace_bytes": (_SZ, [_I64, _I32]),
+    "o3dx_orient_normals_tangent_plane": (_I32, [_P, _I64, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
 }
 
 _lib = None

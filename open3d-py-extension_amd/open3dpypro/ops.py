@@ -406,6 +406,63 @@ def dbscan(xyz: torch.Tensor, eps: float, min_samples: int, return_core: bool = 
     return labels, int(cnt[0])
 
 
+def emst(xyz: torch.Tensor) -> torch.Tensor:
+    """The Euclidean minimum spanning tree of the points (o3dx_emst): an
+    (n - 1, 2) int32 device tensor of {lo, hi} rows, lo < hi, sorted by
+    (lo, hi).  Weights are the float64 d^2 of the float32 coordinates; edges
+    are compared by (d^2, lo, hi), so the tree is unique even with duplicate
+    points.  float32 points only."""
+    if _is64(xyz):
+        raise NotImplementedError("emst: float64 clouds are outside this implementation (float32 points only)")
+    x = _xyz(xyz)
+    n = x.shape[0]
+    dev = x.device
+    edges = torch.empty((max(n - 1, 0), 2), dtype=torch.int32, device=dev)
+    if n < 2:
+        return edges
+    L = N.load()
+    ws = N.workspace(L.o3dx_emst_workspace_bytes(n), dev)
+    N.check(L.o3dx_emst(N.ptr(x), n, None, 0, N.ptr(edges), N.ptr(ws), ws.numel(), N.stream_ptr(dev)), "emst")
+    return edges
+
+
+def orient_normals_tangent_plane(xyz: torch.Tensor, normals: torch.Tensor, k: int, return_tree: bool = False):
+    """Open3D OrientNormalsConsistentTangentPlane(k) on the device
+    (o3dx_orient_normals_tangent_plane; include/o3dx.h states the rule):
+    the oriented normals, a new (n, 3) float32 tensor whose rows are the
+    input's or their negation (sign bits only).  return_tree: also the
+    (n - 1, 2) int32 tree edges sorted by (lo, hi) and the (n,) bool flips.
+    The neighbour lists are knn_search's (min(k, n) nearest, the point itself
+    included; at most MAX_KNN).  ValueError for k < 1; float32 points only."""
+    if int(k) != k or int(k) < 1:
+        raise ValueError(f"k must be an int >= 1, got {k}")
+    if _is64(xyz):
+        raise NotImplementedError("orient_normals_tangent_plane: float64 clouds are outside this implementation "
+                                  "(float32 points only)")
+    x = _xyz(xyz)
+    nrm = _xyz(normals, "normals")
+    n = x.shape[0]
+    if nrm.shape[0] != n:
+        raise RuntimeError(f"normals must have one row per point ({n}), got {nrm.shape[0]}")
+    dev = x.device
+    out = nrm.clone()
+    tree = torch.empty((max(n - 1, 0), 2), dtype=torch.int32, device=dev)
+    flipped = torch.zeros(n, dtype=torch.uint8, device=dev)
+    if n > 0:
+        kk = min(int(k), n)
+        idx, _, _ = knn_search(x, x, N.SEARCH_KNN, kk)
+        idx = idx.contiguous()
+        L = N.load()
+        ws = N.workspace(L.o3dx_orient_normals_workspace_bytes(n, kk), dev)
+        N.check(L.o3dx_orient_normals_tangent_plane(N.ptr(x), n, N.ptr(idx), kk, N.ptr(out),
+                                                    N.ptr(tree) if return_tree and n > 1 else None,
+                                                    N.ptr(flipped) if return_tree else None, N.ptr(ws), ws.numel(),
+                                                    N.stream_ptr(dev)), "orient_normals_tangent_plane")
+    if return_tree:
+        return out, tree, flipped.bool()
+    return out
+
+
 def raster2d_size(resolution: float, minx: float, miny: float, maxx: float, maxy: float):
     """(w, h) of the reference's to_2D_Img image for these x / y bounds
     (o3dx_raster2d_size, host only; either may be 0)."""
