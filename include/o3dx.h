@@ -963,6 +963,55 @@ int o3dx_orient_normals_tangent_plane(const float* xyz_dev, int64_t n, const int
                                       float* normals_inout_dev, int32_t* tree_out_dev, uint8_t* flipped_out_dev,
                                       void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- LAS IO
+ * LAS 1.0-1.4 point records, uncompressed, on the device; additive to ABI 7.
+ * Replaces the laspy record handling behind the reference's LAS methods
+ * (reference PointCloud.py:496-567: read_las / read_las_gen 523-547,
+ * get_lasdata / append_save_las / save_las 499-521, 549-565).  The host parses
+ * and writes the public header (las_io.py); records are `stride` bytes each
+ * (the header's record length: at least the format's minimum, any extra bytes
+ * are skipped on reading and zero on writing; no alignment needed).  In every
+ * format X, Y, Z are int32 at 0, 4, 8 and the intensity a u16 at 12; the
+ * classification byte is at 15 (formats 0-5) or 16 (6-10); red, green, blue
+ * are u16 at 20 (format 2), 28 (3, 5) or 30 (7, 8, 10).  scale_host /
+ * offset_host: 3 doubles each, finite, scale non-zero.
+ *
+ * o3dx_las_unpack (formats 0..10): per record and axis
+ *   x = (double)X * scale + offset      (one multiply, then one add; no fma)
+ * into xyz64_out_dev ((n,3) float64) and, rounded once, xyz32_out_dev ((n,3)
+ * float32); intensity_out_dev (n) the raw u16; cls_out_dev (n) the whole
+ * classification byte (laspy's raw_classification for formats 0-5; byte 16 for
+ * 6+, where laspy has no such field); rgb_out_dev ((n,3) float32) = u16 / 65536
+ * (exact).  Every output is nullable.  flags_dev (nullable, one u32) is
+ * cleared, then gets O3DX_LAS_FLAG_NOT_F32 when some x is not a float32 value
+ * (NaN does not count).  EINVAL for a format outside 0..10, a stride below
+ * the format's minimum or above 65535, and rgb_out_dev on a format without
+ * colour.  n = 0 is allowed.  Enqueues only.
+ *
+ * o3dx_las_pack (formats 0..3, 6..8): rec_out_dev (n * stride bytes) is
+ * zero-filled and receives, per record and axis,
+ *   X = rint((x - offset) / scale)      (float64, ties to even: np.round)
+ * from xyz_dev ((n,3) float64 when xyz_f64, else float32 upcast exactly);
+ * rgb_dev ((n,3) float32, nullable) as (uint8)(c * 255.0) — the product in
+ * float64, truncated — stored in the u16 colour fields, as the reference's
+ * get_lasdata does (so a colour read back through / 65536 is dimmed 256-fold);
+ * intensity_dev (n u16, nullable) and cls_dev (n u8, nullable) as they are.
+ * stats_dev, 8 int64: {min X, min Y, min Z, max X, max Y, max Z} over the
+ * values that fit int32 (INT32_MAX / INT32_MIN when there is none), the count
+ * of values outside int32 and the count of non-finite values (both are stored
+ * as 0 in the record).  EINVAL as above, and for rgb_dev on a format without
+ * colour.  n = 0 is allowed (the statistics are still initialised).  Enqueues
+ * only: the caller waits when it reads the statistics. */
+#define O3DX_LAS_FLAG_NOT_F32 1u
+int o3dx_las_unpack(const uint8_t* rec_dev, int64_t n, int64_t stride, int point_format, const double* scale_host,
+                    const double* offset_host, double* xyz64_out_dev, float* xyz32_out_dev,
+                    uint16_t* intensity_out_dev, uint8_t* cls_out_dev, float* rgb_out_dev, uint32_t* flags_dev,
+                    void* stream);
+int o3dx_las_pack(const void* xyz_dev, int xyz_f64, int64_t n, int64_t stride, int point_format,
+                  const double* scale_host, const double* offset_host, const float* rgb_dev,
+                  const uint16_t* intensity_dev, const uint8_t* cls_dev, uint8_t* rec_out_dev, int64_t* stats_dev,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,9 +22,14 @@ simple_seg_connected_components_by_img; the reference's cv2 labelling) run on
 the GPU too: ops.raster2d / ccl2d / label_group.  estimate_normals(method=
 "poisson") orients the stored normals on the GPU (Open3D's
 orient_normals_consistent_tangent_plane: ops.orient_normals_tangent_plane).
+LAS files (read_las, read_las_gen, save_las, append_save_las, pcd2las:
+PointCloudAdvanceIO, las_io.py) are decoded and encoded on the GPU
+(ops.las_unpack / las_pack) and by numpy without one.
 Out of scope (SURVEY.md §2
-row 5) and not mirrored: the colour-cosine selections, and the reference's
-other cv2 methods (detect_3d_circles, read_single_RGB).
+row 5) and not mirrored: the colour-cosine selections, the reference's
+other cv2 methods (detect_3d_circles, read_single_RGB), compressed LAZ, E57
+(read_e57*, save_e57, e572las), get_lasdata (it returns laspy objects) and the
+image I/O (save_png / save_jpg / save_tiff).
 """
 from __future__ import annotations
 
@@ -35,7 +40,7 @@ from typing import Callable, List, Tuple
 import numpy as np
 import torch
 
-from . import ops, pcd_io
+from . import las_io, ops, pcd_io
 from . import _native as N
 from .params import KDTreeSearchParamKNN, resolve, resolve_estimation
 
@@ -888,7 +893,170 @@ class PointCloudUtility(PointCloudSelections):
         return a, b, cc, -float((c * v[-1]).sum())
 
 
-class PointCloud(PointCloudUtility):
+class PointCloudAdvanceIO(PointCloudUtility):
+    """LAS I/O (reference PointCloud.py:496-567, 705-710) without laspy:
+    las_io.py holds the format rules; with a GPU the records are decoded and
+    encoded by o3dx_las_unpack / o3dx_las_pack, without one by the numpy forms
+    of the same rules (identical values).  get_lasdata is not mirrored: it
+    returns laspy objects.  E57 (read_e57*, save_e57, e572las), compressed LAZ
+    and the image I/O are out of scope."""
+
+    def get_lasdata(self, *args, **kwargs):
+        """Not mirrored: the reference returns a laspy.LasData (PointCloud.py:
+        499-521), and this package has no laspy.  save_las / append_save_las
+        fill the records by the same rules."""
+        raise NotImplementedError("get_lasdata returns laspy objects and is not mirrored; use save_las / "
+                                  "append_save_las")
+
+    def _las_cloud(self, raw: np.ndarray, h, rgb: bool, intensity: bool, labels: bool):
+        """A new cloud from a block of LAS records."""
+        c = self.__class__()
+        if raw.size == 0:
+            return c
+        if torch.cuda.is_available():
+            d = las_io.decode_device(raw, h, _device(), rgb, intensity, labels)
+            # the kernel's flag makes _wide known without set_points' passes; a
+            # wide cloud keeps its float64 device copy, as set_points' torch branch
+            c._pts = d["points32"]
+            c._wide = d["wide"]
+            c._pts64 = d["points64"]
+            if rgb:
+                c._colors = d["rgb"]
+        else:
+            d = las_io.decode_host(raw, h, rgb, intensity, labels)
+            c.set_points(d["points"])
+            if rgb:
+                c.set_rgb(d["rgb"])
+        if intensity:
+            c.set_intensity(d["intensity"])
+        if labels:
+            c.set_labels(d["labels"])
+        return c
+
+    @staticmethod
+    def _las_header(path: str, rgb: bool):
+        h = las_io.read_header(path)
+        if rgb and not h.has_rgb:
+            raise ValueError(f"{path}: point format {h.point_format} has no colour (rgb=True)")
+        return h
+
+    def read_las(self, path: str, rgb: bool = False, intensity: bool = False, labels: bool = False):
+        """A new cloud from a LAS 1.0-1.4 file, point formats 0-10,
+        uncompressed (reference PointCloud.py:523-533).  Points are the
+        float64 X * scale + offset; such values are rarely float32 values, so
+        the cloud usually runs the float64 kernels (_wide).  rgb: colours
+        u16 / 65536 (ValueError when the format has none); intensity: (n,1)
+        uint16; labels: (n,1) uint8, the whole classification byte — laspy's
+        raw_classification for formats 0-5, byte 16 for formats 6+ (this
+        project's rule: laspy has no raw_classification there).  With a GPU
+        the file's records go to the device once and are decoded there.
+        RuntimeError names the file and the reason for a bad signature, an
+        unknown or compressed (LAZ) point format, a record length below the
+        format's minimum and truncated point data."""
+        h = self._las_header(path, rgb)
+        return self._las_cloud(las_io.read_records(h), h, rgb, intensity, labels)
+
+    def read_las_gen(self, path: str, every_k_points: int = 100_0000, rgb: bool = False, intensity: bool = False,
+                     labels: bool = False):
+        """read_las in chunks (reference PointCloud.py:535-547): a generator of
+        clouds of at most every_k_points consecutive records, each read from
+        the file and decoded on its own; the file is never resident at once."""
+        k = int(every_k_points)
+        if k < 1:
+            raise ValueError(f"every_k_points must be >= 1, got {every_k_points}")
+        h = self._las_header(path, rgb)
+        count = 0
+        while count < h.count:
+            m = min(k, h.count - count)
+            pcd = self._las_cloud(las_io.read_records(h, count, m), h, rgb, intensity, labels)
+            count += m
+            print(f"[read_las_gen]: read {count / h.count * 100}% points.")
+            yield pcd
+
+    def _las_records(self, what: str, point_format: int, stride: int, scales, offsets, float32_coords: bool):
+        """(records (n, stride) uint8 numpy, stats) of this cloud; raises before
+        anything is written."""
+        if self.has_rgb() and las_io.LAYOUT[point_format][2] is None:
+            raise ValueError(f"{what}: the cloud has colours and point format {point_format} has none")
+        # the reference's conversions (get_lasdata, PointCloud.py:511-512, 519-520), on the host
+        inten = cls = None
+        if self.has_intensity():
+            inten = (np.asarray(self.get_intensity()).flatten() * 255).astype(np.uint8).astype(np.uint16)
+        if self.has_labels():
+            cls = np.asarray(self.labels).flatten().astype(np.uint8)
+        if torch.cuda.is_available():
+            dev = _device()
+            x = self._dev_points() if float32_coords else self._hot_points()
+            up = lambda a: None if a is None else torch.from_numpy(a).to(dev)  # noqa: E731
+            rec, stats = ops.las_pack(x, stride, point_format, scales, offsets,
+                                      rgb=self._colors.to(dev) if self.has_rgb() else None,
+                                      intensity=up(None if inten is None else inten.view(np.int16)), labels=up(cls))
+            stats = stats.cpu().numpy()
+            las_io.check_stats(stats, what)
+            return rec.cpu().numpy(), stats
+        pts = self._dev_points().numpy() if float32_coords else self.get_points()
+        rec, stats = las_io.pack_host(pts, point_format, stride, scales, offsets,
+                                      rgb=self._colors.numpy() if self.has_rgb() else None, intensity=inten,
+                                      labels=cls)
+        las_io.check_stats(stats, what)
+        return rec, stats
+
+    def save_las(self, path: str = './pcd.las', pt_src_id: bool = False, *, scales=None, offsets=None,
+                 point_format: int = 3, float32_coords: bool = True):
+        """Write the cloud as LAS 1.2 (reference PointCloud.py:560-565).  The
+        defaults reproduce the reference: point format 3, scales 1e-4, offsets
+        0, coordinates cast to float32 first (get_lasdata's
+        ps[:, 0].astype(np.float32)).  float32_coords=False quantises the
+        cloud's float64 values directly, so a georeferenced cloud can be
+        written with suitable offsets.  X = np.round((x - offset) / scale).
+        Colours are written as (uint8)(c * 255) into the u16 fields and
+        intensity as (uint8)(i * 255), the reference's conversions: read_las
+        returns such a colour 256-fold dimmed (c * 255 / 65536), and an
+        intensity i as int(i * 255) mod 256.  point_format: 0-3 or 6-8.
+        OverflowError when a scaled coordinate leaves int32 (as laspy),
+        ValueError for non-finite coordinates (this project's rule); in both
+        cases nothing is written.  pt_src_id=True needs the E57 object:
+        NotImplementedError."""
+        if pt_src_id:
+            raise NotImplementedError("save_las(pt_src_id=True) needs the E57 scan index (E57 is not mirrored)")
+        if point_format not in las_io.WRITABLE:
+            raise ValueError(f"save_las: point format {point_format} cannot be written (only {las_io.WRITABLE})")
+        sc = np.full(3, 1e-4) if scales is None else np.broadcast_to(np.asarray(scales, np.float64), (3,)).copy()
+        of = np.zeros(3) if offsets is None else np.broadcast_to(np.asarray(offsets, np.float64), (3,)).copy()
+        if not (np.isfinite(sc).all() and (sc != 0).all() and np.isfinite(of).all()):
+            raise ValueError("save_las: scales must be finite and non-zero, offsets finite")
+        stride = las_io.LAYOUT[point_format][0]
+        rec, stats = self._las_records(f"save_las({path})", point_format, stride, sc, of, float32_coords)
+        las_io.write_file(path, las_io.build_header(point_format, stride, len(rec), sc, of, stats), rec)
+
+    def append_save_las(self, path: str = './pcd.las', pt_src_id: bool = False):
+        """Append the cloud to an existing LAS file (reference PointCloud.py:
+        549-558) with that file's point format, record length, scales and
+        offsets; the point count (legacy, and the u64 count of LAS 1.4) and the
+        merged min / max are rewritten.  AssertionError when the file does not
+        exist; RuntimeError when bytes follow the point block (EVLRs) or the
+        format is not one save_las writes; on OverflowError / ValueError the
+        file is left as it was."""
+        assert os.path.isfile(path), f'file {path} is no exist.'
+        if pt_src_id:
+            raise NotImplementedError("append_save_las(pt_src_id=True) needs the E57 scan index (E57 is not mirrored)")
+        h = las_io.read_header(path)
+        las_io.check_appendable(h)
+        rec, stats = self._las_records(f"append_save_las({path})", h.point_format, h.stride, h.scales, h.offsets, True)
+        las_io.append_records(h, rec, stats)
+
+    def pcd2las(self, from_path: str, to_path: str = None):
+        """The reference's two-step converter (PointCloud.py:705-710): a
+        generator yielding 0.5 after reading the PCD and 1.0 after save_las."""
+        if to_path is None:
+            to_path = from_path.replace('.pcd', '.las')
+        p = self.read_pcd(from_path)
+        yield 0.5
+        p.save_las(to_path)
+        yield 1.0
+
+
+class PointCloud(PointCloudAdvanceIO):
 
     def split_pcd_index(self, nn: int, random: bool = False):
         n = self.size()

@@ -172,6 +172,9 @@ _SIGS = {
     "o3dx_emst": (_I32, [_P, _I64, _P, _I32, _P, _P, _SZ, _P]),
     "o3dx_orient_normals_workspace_bytes": (_SZ, [_I64, _I32]),
     "o3dx_orient_normals_tangent_plane": (_I32, [_P, _I64, _P, _I32, _P, _P, _P, _P, _SZ, _P]),
+    # LAS point records (additive to ABI 7)
+    "o3dx_las_unpack": (_I32, [_P, _I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "o3dx_las_pack": (_I32, [_P, _I32, _I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -556,6 +556,68 @@ def label_group(pix: torch.Tensor, labels: torch.Tensor, k: int):
     return point_label, order, counts
 
 
+def las_unpack(records: torch.Tensor, n: int, stride: int, point_format: int, scales, offsets, rgb: bool = False,
+               intensity: bool = False, labels: bool = False):
+    """LAS point records decoded on the device (o3dx_las_unpack;
+    include/o3dx.h states the layout and the rules).  records: a uint8 device
+    tensor of at least n * stride bytes.  Returns a dict of device tensors:
+    points64 (n,3) float64 = X * scale + offset, points32 (n,3) float32, flags
+    (1,) int32 (bit 0: some coordinate is not a float32 value), and when asked
+    for rgb (n,3) float32 = u16 / 65536, intensity (n,) int16 holding the raw
+    u16 bits, labels (n,) uint8 (the whole classification byte).  No host
+    wait: reading flags is the caller's."""
+    N.require_device(records, "records")
+    n, stride = int(n), int(stride)
+    if records.dtype != torch.uint8 or n < 0 or records.numel() < n * stride:
+        raise RuntimeError(f"records must be a uint8 tensor of >= n * stride = {n * stride} bytes, got "
+                           f"{records.dtype} x {records.numel()}")
+    rec = records.contiguous()
+    dev = rec.device
+    p64 = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    p32 = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    flags = torch.empty(1, dtype=torch.int32, device=dev)
+    col = torch.empty((n, 3), dtype=torch.float32, device=dev) if rgb else None
+    inten = torch.empty(n, dtype=torch.int16, device=dev) if intensity else None
+    cls = torch.empty(n, dtype=torch.uint8, device=dev) if labels else None
+    sc, of = _c(scales, np.float64).reshape(3), _c(offsets, np.float64).reshape(3)
+    N.check(N.load().o3dx_las_unpack(N.ptr(rec), n, stride, int(point_format), _np_ptr(sc), _np_ptr(of), N.ptr(p64),
+                                     N.ptr(p32), N.ptr(inten), N.ptr(cls), N.ptr(col), N.ptr(flags),
+                                     N.stream_ptr(dev)), "las_unpack")
+    return {"points64": p64, "points32": p32, "flags": flags, "rgb": col, "intensity": inten, "labels": cls}
+
+
+def las_pack(xyz: torch.Tensor, stride: int, point_format: int, scales, offsets, rgb: Optional[torch.Tensor] = None,
+             intensity: Optional[torch.Tensor] = None, labels: Optional[torch.Tensor] = None):
+    """LAS point records encoded on the device (o3dx_las_pack): xyz (n,3)
+    float32 or float64, rgb (n,3) float32 in [0,1], intensity (n,) int16 /
+    uint16 bits, labels (n,) uint8.  Returns (records (n, stride) uint8,
+    stats (8,) int64 {min X Y Z, max X Y Z, values outside int32, non-finite
+    values}), both on the device and not waited for."""
+    f64 = _is64(xyz)
+    x = _xyz64(xyz) if f64 else _xyz(xyz)
+    n, stride = int(x.shape[0]), int(stride)
+    dev = x.device
+
+    def opt(t, dtypes, shape, what):
+        if t is None:
+            return None
+        N.require_device(t, what)
+        if t.dtype not in dtypes or tuple(t.shape) != shape:
+            raise RuntimeError(f"{what} must be {dtypes[0]} of shape {shape}, got {t.dtype} {tuple(t.shape)}")
+        return t.contiguous()
+
+    col = opt(rgb, (torch.float32,), (n, 3), "rgb")
+    inten = opt(intensity, (torch.int16, getattr(torch, "uint16", torch.int16)), (n,), "intensity")
+    cls = opt(labels, (torch.uint8,), (n,), "labels")
+    rec = torch.empty((n, max(stride, 0)), dtype=torch.uint8, device=dev)
+    stats = torch.empty(8, dtype=torch.int64, device=dev)
+    sc, of = _c(scales, np.float64).reshape(3), _c(offsets, np.float64).reshape(3)
+    N.check(N.load().o3dx_las_pack(N.ptr(x), 1 if f64 else 0, n, stride, int(point_format), _np_ptr(sc), _np_ptr(of),
+                                   N.ptr(col), N.ptr(inten), N.ptr(cls), N.ptr(rec), N.ptr(stats),
+                                   N.stream_ptr(dev)), "las_pack")
+    return rec, stats
+
+
 def ransac_samples(n: int, ransac_n: int, num_iterations: int, seed: int) -> np.ndarray:
     """Open3D RandomSampler over mt19937(seed): (iters, ransac_n) int32."""
     out = np.empty((max(num_iterations, 1), ransac_n), np.int32)
