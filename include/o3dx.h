@@ -114,9 +114,19 @@ int o3dx_search_stats(int64_t* out8_host);
  * eigenvectors (m,3) f64 (dev).  Asynchronous.
  *
  * o3dx_libm_probe: the device double-precision function the normals use
- * (fn 0 = acos, 1 = cos, 2 = sqrt) on n values (dev) -> out (dev). */
+ * (fn 0 = acos, 1 = cos, 2 = sqrt) on n values (dev) -> out (dev).
+ *
+ * o3dx_normal_finish_check (additive to ABI 7): the normals kernels' finish,
+ * covariance tail + FastEigen3x3, on m sets of nine raw moments {x, y, z, xx,
+ * xy, xz, yy, yz, zz} (m,9) f64 (dev) of k >= 1 points each -> covariances
+ * {xx,xy,xz,yy,yz,zz} (m,6) and eigenvectors (m,3), f64 (dev).  ref = 0 runs
+ * the product formulation (selects, shared-divisor exact division), ref != 0
+ * Open3D's text (an arm per case, a division per quotient); the two must
+ * agree bit for bit.  Asynchronous. */
 int o3dx_set_debug_neighbors(int32_t* buf_dev, int64_t rows, int k);
 int o3dx_fast_eigen3x3(const double* cov_dev, int64_t m, double* out_dev, void* stream);
+int o3dx_normal_finish_check(const double* mom9_dev, int64_t m, int k, int ref, double* cov6_out_dev,
+                             double* vec3_out_dev, void* stream);
 int o3dx_libm_probe(const double* x_dev, int64_t n, int fn, double* out_dev, void* stream);
 
 /* ---------------------------------------------------------------- AABB

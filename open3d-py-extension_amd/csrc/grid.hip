@@ -9,6 +9,7 @@
 #include <type_traits>
 #include <utility>
 
+#include "eigen3.hpp"
 #include "grid.hpp"
 
 namespace o3dx {
@@ -627,154 +628,7 @@ int chunk_plan(int64_t n, const GridView& g, int qcap, int32_t* chunk_starts, vo
   return 0;
 }
 
-// ------------------------------------------------------- FastEigen3x3 (f64)
-__device__ __forceinline__ void dcross(const double u[3], const double v[3], double o[3]) {
-  o[0] = u[1] * v[2] - u[2] * v[1];
-  o[1] = u[2] * v[0] - u[0] * v[2];
-  o[2] = u[0] * v[1] - u[1] * v[0];
-}
-__device__ __forceinline__ double ddot(const double u[3], const double v[3]) {
-  return (u[0] * v[0] + u[1] * v[1]) + u[2] * v[2];
-}
-
-// Open3D ComputeEigenvector0
-__device__ void eigvec0(const double A[3][3], double e, double out[3]) {
-  double r0[3] = {A[0][0] - e, A[0][1], A[0][2]};
-  double r1[3] = {A[0][1], A[1][1] - e, A[1][2]};
-  double r2[3] = {A[0][2], A[1][2], A[2][2] - e};
-  double a[3], b[3], c[3];
-  dcross(r0, r1, a);
-  dcross(r0, r2, b);
-  dcross(r1, r2, c);
-  double d0 = ddot(a, a), d1 = ddot(b, b), d2 = ddot(c, c);
-  double dmax = d0;
-  int imax = 0;
-  if (d1 > dmax) {
-    dmax = d1;
-    imax = 1;
-  }
-  if (d2 > dmax) imax = 2;
-  if (imax == 0) {
-    double s = sqrt(d0);
-    out[0] = a[0] / s; out[1] = a[1] / s; out[2] = a[2] / s;
-  } else if (imax == 1) {
-    double s = sqrt(d1);
-    out[0] = b[0] / s; out[1] = b[1] / s; out[2] = b[2] / s;
-  } else {
-    double s = sqrt(d2);
-    out[0] = c[0] / s; out[1] = c[1] / s; out[2] = c[2] / s;
-  }
-}
-
-// Open3D ComputeEigenvector1
-__device__ void eigvec1(const double A[3][3], const double e0[3], double e1v, double out[3]) {
-  double U[3], V[3];
-  if (fabs(e0[0]) > fabs(e0[1])) {
-    double inv = 1.0 / sqrt(e0[0] * e0[0] + e0[2] * e0[2]);
-    U[0] = -e0[2] * inv; U[1] = 0; U[2] = e0[0] * inv;
-  } else {
-    double inv = 1.0 / sqrt(e0[1] * e0[1] + e0[2] * e0[2]);
-    U[0] = 0; U[1] = e0[2] * inv; U[2] = -e0[1] * inv;
-  }
-  dcross(e0, U, V);
-  double AU[3] = {A[0][0] * U[0] + A[0][1] * U[1] + A[0][2] * U[2], A[0][1] * U[0] + A[1][1] * U[1] + A[1][2] * U[2],
-                  A[0][2] * U[0] + A[1][2] * U[1] + A[2][2] * U[2]};
-  double AV[3] = {A[0][0] * V[0] + A[0][1] * V[1] + A[0][2] * V[2], A[0][1] * V[0] + A[1][1] * V[1] + A[1][2] * V[2],
-                  A[0][2] * V[0] + A[1][2] * V[1] + A[2][2] * V[2]};
-  double m00 = U[0] * AU[0] + U[1] * AU[1] + U[2] * AU[2] - e1v;
-  double m01 = U[0] * AV[0] + U[1] * AV[1] + U[2] * AV[2];
-  double m11 = V[0] * AV[0] + V[1] * AV[1] + V[2] * AV[2] - e1v;
-  double a00 = fabs(m00), a01 = fabs(m01), a11 = fabs(m11);
-  if (a00 >= a11) {
-    if (fmax(a00, a01) > 0) {
-      if (a00 >= a01) {
-        m01 /= m00; m00 = 1 / sqrt(1 + m01 * m01); m01 *= m00;
-      } else {
-        m00 /= m01; m01 = 1 / sqrt(1 + m00 * m00); m00 *= m01;
-      }
-      for (int i = 0; i < 3; ++i) out[i] = m01 * U[i] - m00 * V[i];
-    } else {
-      for (int i = 0; i < 3; ++i) out[i] = U[i];
-    }
-  } else {
-    if (fmax(a11, a01) > 0) {
-      if (a11 >= a01) {
-        m01 /= m11; m11 = 1 / sqrt(1 + m01 * m01); m01 *= m11;
-      } else {
-        m11 /= m01; m01 = 1 / sqrt(1 + m11 * m11); m11 *= m01;
-      }
-      for (int i = 0; i < 3; ++i) out[i] = m11 * U[i] - m01 * V[i];
-    } else {
-      for (int i = 0; i < 3; ++i) out[i] = U[i];
-    }
-  }
-}
-
-// Open3D FastEigen3x3 (Eberly's robust symmetric 3x3 solver): smallest eigenvector.
-// c = {xx, xy, xz, yy, yz, zz}
-__device__ void fast_eigen3x3(const double c[6], double out[3]) {
-  double A[3][3] = {{c[0], c[1], c[2]}, {c[1], c[3], c[4]}, {c[2], c[4], c[5]}};
-  double max_coeff = A[0][0];
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) max_coeff = fmax(max_coeff, A[i][j]);
-  if (max_coeff == 0) {
-    out[0] = out[1] = out[2] = 0;
-    return;
-  }
-  for (int i = 0; i < 3; ++i)
-    for (int j = 0; j < 3; ++j) A[i][j] /= max_coeff;
-  double norm = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
-  if (norm > 0) {
-    double q = (A[0][0] + A[1][1] + A[2][2]) / 3;
-    double b00 = A[0][0] - q, b11 = A[1][1] - q, b22 = A[2][2] - q;
-    double p = sqrt((b00 * b00 + b11 * b11 + b22 * b22 + norm * 2) / 6);
-    double c00 = b11 * b22 - A[1][2] * A[1][2];
-    double c01 = A[0][1] * b22 - A[1][2] * A[0][2];
-    double c02 = A[0][1] * A[1][2] - b11 * A[0][2];
-    double det = (b00 * c00 - A[0][1] * c01 + A[0][2] * c02) / (p * p * p);
-    double half_det = fmin(fmax(det * 0.5, -1.0), 1.0);
-    double angle = acos(half_det) / (double)3;
-    const double two_thirds_pi = 2.09439510239319549;
-    double beta2 = cos(angle) * 2;
-    double beta0 = cos(angle + two_thirds_pi) * 2;
-    double beta1 = -(beta0 + beta2);
-    double ev0 = q + p * beta0, ev1 = q + p * beta1, ev2 = q + p * beta2;
-    double ea[3], eb[3];
-    if (half_det >= 0) {
-      eigvec0(A, ev2, ea);
-      if (ev2 < ev0 && ev2 < ev1) {
-        out[0] = ea[0]; out[1] = ea[1]; out[2] = ea[2];
-        return;
-      }
-      eigvec1(A, ea, ev1, eb);
-      if (ev1 < ev0 && ev1 < ev2) {
-        out[0] = eb[0]; out[1] = eb[1]; out[2] = eb[2];
-        return;
-      }
-      dcross(eb, ea, out);  // evec0 = evec1 x evec2
-    } else {
-      eigvec0(A, ev0, ea);
-      if (ev0 < ev1 && ev0 < ev2) {
-        out[0] = ea[0]; out[1] = ea[1]; out[2] = ea[2];
-        return;
-      }
-      eigvec1(A, ea, ev1, eb);
-      if (ev1 < ev0 && ev1 < ev2) {
-        out[0] = eb[0]; out[1] = eb[1]; out[2] = eb[2];
-        return;
-      }
-      dcross(ea, eb, out);  // evec2 = evec0 x evec1
-    }
-  } else {
-    if (A[0][0] < A[1][1] && A[0][0] < A[2][2]) {
-      out[0] = 1; out[1] = 0; out[2] = 0;
-    } else if (A[1][1] < A[0][0] && A[1][1] < A[2][2]) {
-      out[0] = 0; out[1] = 1; out[2] = 0;
-    } else {
-      out[0] = 0; out[1] = 0; out[2] = 1;
-    }
-  }
-}
+// FastEigen3x3 and the covariance tail (f64): eigen3.hpp, shared with the host test
 
 struct MomAcc {
   double m[9];
@@ -798,17 +652,7 @@ struct MomAcc {
     m[7] = fma(y, z, m[7]);
     m[8] = fma(z, z, m[8]);
   }
-  __device__ void cov(int k, double c[6]) const {
-    double u[9];
-#pragma unroll
-    for (int j = 0; j < 9; ++j) u[j] = m[j] / (double)k;
-    c[0] = u[3] - u[0] * u[0];
-    c[3] = u[6] - u[1] * u[1];
-    c[5] = u[8] - u[2] * u[2];
-    c[1] = u[4] - u[0] * u[1];
-    c[2] = u[5] - u[0] * u[2];
-    c[4] = u[7] - u[1] * u[2];
-  }
+  __device__ void cov(int k, double c[6]) const { moments_cov(m, k, c); }
 };
 
 // Exact-sum form of MomAcc for the sorted-grid kernels: each moment is a
@@ -3682,6 +3526,25 @@ __global__ void __launch_bounds__(kBlock) k_fast_eigen(const double* __restrict_
   for (int j = 0; j < 3; ++j) out[3 * i + j] = v[j];
 }
 
+// the product finish (REF = false) or its *_ref yardstick on m moment sets
+template <bool REF>
+__global__ void __launch_bounds__(kBlock) k_normal_finish_check(const double* __restrict__ mom, int64_t m, int k,
+                                                                double* __restrict__ cov, double* __restrict__ vec) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  double mm[9], c[6], v[3];
+  for (int j = 0; j < 9; ++j) mm[j] = mom[9 * i + j];
+  if (REF) {
+    moments_cov_ref(mm, k, c);
+    fast_eigen3x3_ref(c, v);
+  } else {
+    moments_cov(mm, k, c);
+    fast_eigen3x3(c, v);
+  }
+  for (int j = 0; j < 6; ++j) cov[6 * i + j] = c[j];
+  for (int j = 0; j < 3; ++j) vec[3 * i + j] = v[j];
+}
+
 __global__ void __launch_bounds__(kBlock) k_libm_probe(const double* __restrict__ x, int64_t n, int fn,
                                                        double* __restrict__ out) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -3695,6 +3558,22 @@ extern "C" int o3dx_fast_eigen3x3(const double* cov, int64_t m, double* out, voi
   if (m == 0) return 0;
   hipLaunchKernelGGL(k_fast_eigen, dim3((unsigned)((m + kBlock - 1) / kBlock)), dim3(kBlock), 0, as_stream(stream),
                      cov, m, out);
+  O3DX_HIP(hipGetLastError());
+  return 0;
+}
+
+extern "C" int o3dx_normal_finish_check(const double* mom9, int64_t m, int k, int ref, double* cov6_out,
+                                        double* vec3_out, void* stream) {
+  if (m < 0 || k < 1 || (m > 0 && (!mom9 || !cov6_out || !vec3_out)))
+    return fail(O3DX_EINVAL, "o3dx_normal_finish_check: bad arguments");
+  if (m == 0) return 0;
+  const dim3 grid((unsigned)((m + kBlock - 1) / kBlock));
+  if (ref)
+    hipLaunchKernelGGL(k_normal_finish_check<true>, grid, dim3(kBlock), 0, as_stream(stream), mom9, m, k, cov6_out,
+                       vec3_out);
+  else
+    hipLaunchKernelGGL(k_normal_finish_check<false>, grid, dim3(kBlock), 0, as_stream(stream), mom9, m, k, cov6_out,
+                       vec3_out);
   O3DX_HIP(hipGetLastError());
   return 0;
 }

@@ -49,6 +49,7 @@ _SIGS = {
     "o3dx_set_debug_neighbors": (_I32, [_P, _I64, _I32]),
     "o3dx_fast_eigen3x3": (_I32, [_P, _I64, _P, _P]),
     "o3dx_libm_probe": (_I32, [_P, _I64, _I32, _P, _P]),
+    "o3dx_normal_finish_check": (_I32, [_P, _I64, _I32, _I32, _P, _P, _P]),
     "o3dx_aabb_workspace_bytes": (_SZ, [_I64]),
     "o3dx_aabb": (_I32, [_P, _I64, _P, _P, _SZ, _P]),
     "o3dx_aabb_device": (_I32, [_P, _I64, _P, _P, _SZ, _P]),
