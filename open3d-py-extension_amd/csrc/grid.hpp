@@ -108,21 +108,27 @@ __device__ __forceinline__ double dist2_f64(double qx, double qy, double qz, flo
 }
 
 // Visit every cell of Chebyshev shell r around (cx,cy,cz); f(cell) per cell.
+// (cx,cy,cz) is a cell of the grid.  The loops run over the part of the shell
+// inside the grid only: on a grid one or a few cells thick (a flat or
+// elongated cloud, two clusters far apart) a query far from the points walks
+// thousands of shells, and stepping through each shell's (2r+1)^2 rows outside
+// the grid made that walk cubic in the shell count.
 template <class F>
 __device__ __forceinline__ void for_shell(const GridView& g, int cx, int cy, int cz, int r, F&& f) {
-  for (int dz = -r; dz <= r; ++dz) {
+  const int z0 = max(-r, -cz), z1 = min(r, g.nz - 1 - cz);
+  const int y0 = max(-r, -cy), y1 = min(r, g.ny - 1 - cy);
+  const int x0 = max(-r, -cx), x1 = min(r, g.nx - 1 - cx);
+  for (int dz = z0; dz <= z1; ++dz) {
     const int z = cz + dz;
-    if (z < 0 || z >= g.nz) continue;
     const bool zf = (dz == -r) || (dz == r);
-    for (int dy = -r; dy <= r; ++dy) {
+    for (int dy = y0; dy <= y1; ++dy) {
       const int y = cy + dy;
-      if (y < 0 || y >= g.ny) continue;
-      const bool face = zf || (dy == -r) || (dy == r);
-      const int step = face ? 1 : 2 * r;
-      for (int dx = -r; dx <= r; dx += step) {
-        const int x = cx + dx;
-        if (x < 0 || x >= g.nx) continue;
-        f(x + g.nx * (y + g.ny * z));
+      const int row = g.nx * (y + g.ny * z);
+      if (zf || (dy == -r) || (dy == r)) {
+        for (int dx = x0; dx <= x1; ++dx) f(cx + dx + row);
+      } else {  // r >= 1: the two ends of the row
+        if (x0 == -r) f(cx - r + row);
+        if (x1 == r) f(cx + r + row);
       }
     }
   }
