@@ -1022,6 +1022,92 @@ int o3dx_las_pack(const void* xyz_dev, int xyz_f64, int64_t n, int64_t stride, i
                   const uint16_t* intensity_dev, const uint8_t* cls_dev, uint8_t* rec_out_dev, int64_t* stats_dev,
                   void* stream);
 
+/* ---------------------------------------------------------------- E57 IO
+ * E57 (ASTM E2807) files on the device; additive to ABI 7.  Replaces the
+ * pye57 / libE57 byte work behind the reference's E57 methods (reference
+ * PointCloud.py:569-703, E57File.py).  The host (e57_io.py) parses and writes
+ * the 48-byte file header, the XML, the section headers and the packet
+ * headers.  The file's bytes are in device memory once, paged as on disk: a
+ * page is 1024 bytes, 1020 of payload and a big-endian CRC32C (Castagnoli:
+ * reflected 0x82F63B78, init and final xor 0xFFFFFFFF) of them; logical
+ * offset l is physical offset l + 4 * (l / 1020).
+ *
+ * o3dx_e57_crc_pages: checks the n_pages pages at file_dev (16-byte aligned);
+ * out2_dev = {bad pages, first bad page or INT64_MAX}.
+ *
+ * o3dx_e57_unpack decodes records [r0, r0 + n) of one scan.  desc_host, 6
+ * int64 per field: {role O3DX_E57_ROLE_*, kind O3DX_E57_KIND_*, bits, minimum,
+ * first segment row, segment rows}; affine_host, 2 doubles per field: {scale,
+ * offset}.  seg_dev: rows {stream byte offset, logical file offset, length} of
+ * the field's bytestream, ascending and gap-free in the stream (the pieces of
+ * it in the data packets), lengths > 0.  Record r of a field of b bits is the
+ * b bits from stream bit r * b, LSB first; bytes that are not contiguous in
+ * the file are fetched one by one, so a value may straddle a page trailer and
+ * a segment end.  Rules:
+ *   Float single widens to float64 exactly; Float double as it is;
+ *   Integer        v = minimum + raw                     (int64, wrapping)
+ *   ScaledInteger  x = (double)v * scale + offset        (one multiply, then
+ *                                                         one add; no fma)
+ *   pose_host (nullable; 12 doubles, R row-major then t):
+ *     x' = ((R00 * x + R01 * y) + R02 * z) + t0          (in that order)
+ * Outputs, each nullable: xyz64 (n,3) float64, xyz32 (n,3) float32 (rounded
+ * once), rgb (n,3) uint8, intensity (n) float32 (an Integer field converts
+ * with one rounding), row / col (n) uint16, invalid (n) int8 — the integer
+ * columns take Integer fields only and keep the low bits.  A field whose
+ * output is null is not decoded.  flags_dev (nullable, one u32) is cleared,
+ * then gets O3DX_E57_FLAG_NOT_F32 when some output coordinate is not a float32
+ * value (NaN does not count) and O3DX_E57_FLAG_RANGE when a record's bytes lie
+ * outside its segments or the file (they read as 0; nothing outside file_dev
+ * is touched).  EINVAL for a role twice, a kind / bits mismatch, segment rows
+ * outside the table and an output without its field(s).  Enqueues only.
+ *
+ * o3dx_e57_pack writes the data packets of one scan, headers included, into
+ * out_dev (4-byte aligned; (packets - 1) * full_bytes + last_bytes bytes,
+ * every byte written).  Packets hold records_per_packet records (a multiple
+ * of 8, so every stream is whole bytes), the last one the rest; head_full_host
+ * / head_last_host are their 6 + 2 * n_fields header bytes.  desc_host, 6
+ * int64 per field: {source O3DX_E57_SRC_*, bits, minimum, stream offset in a
+ * full packet, in the last packet, stream bytes in the last packet}; src_host:
+ * one device pointer per field; stride_host: {element stride, first element}
+ * per field.  Sources: F32 / F64 the value's bits (32 / 64); COLOUR a float32
+ * colour as (uint8)(c * 255.0), the product in float64, truncated (8 bits);
+ * I64 an int64 as value - minimum in `bits` bits (0..64).  Bit-packed streams
+ * are gathered: one lane per output word collects the records overlapping it.
+ *
+ * o3dx_e57_seal lays logical_bytes (a multiple of 4) into n_pages pages at
+ * paged_out_dev, zero-pads the last and writes each page's CRC trailer. */
+#define O3DX_E57_ROLE_X 0
+#define O3DX_E57_ROLE_Y 1
+#define O3DX_E57_ROLE_Z 2
+#define O3DX_E57_ROLE_INTENSITY 3
+#define O3DX_E57_ROLE_RED 4
+#define O3DX_E57_ROLE_GREEN 5
+#define O3DX_E57_ROLE_BLUE 6
+#define O3DX_E57_ROLE_ROW 7
+#define O3DX_E57_ROLE_COLUMN 8
+#define O3DX_E57_ROLE_INVALID 9
+#define O3DX_E57_KIND_F32 0
+#define O3DX_E57_KIND_F64 1
+#define O3DX_E57_KIND_INT 2
+#define O3DX_E57_KIND_SCALED 3
+#define O3DX_E57_SRC_F32 0
+#define O3DX_E57_SRC_F64 1
+#define O3DX_E57_SRC_COLOUR 2
+#define O3DX_E57_SRC_I64 3
+#define O3DX_E57_FLAG_NOT_F32 1u
+#define O3DX_E57_FLAG_RANGE 2u
+int o3dx_e57_crc_pages(const uint8_t* file_dev, int64_t n_pages, int64_t* out2_dev, void* stream);
+int o3dx_e57_unpack(const uint8_t* file_dev, int64_t file_bytes, int n_fields, const int64_t* desc_host,
+                    const double* affine_host, const int64_t* seg_dev, int64_t seg_rows, int64_t r0, int64_t n,
+                    const double* pose_host, double* xyz64_out_dev, float* xyz32_out_dev, uint8_t* rgb_out_dev,
+                    float* intensity_out_dev, uint16_t* row_out_dev, uint16_t* col_out_dev, int8_t* invalid_out_dev,
+                    uint32_t* flags_dev, void* stream);
+int o3dx_e57_pack(int n_fields, const int64_t* desc_host, const void* const* src_host, const int64_t* stride_host,
+                  int64_t n, int64_t records_per_packet, int64_t full_bytes, int64_t last_bytes,
+                  const uint8_t* head_full_host, const uint8_t* head_last_host, uint8_t* out_dev, void* stream);
+int o3dx_e57_seal(const uint8_t* logical_dev, int64_t logical_bytes, uint8_t* paged_out_dev, int64_t n_pages,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,11 +25,16 @@ orient_normals_consistent_tangent_plane: ops.orient_normals_tangent_plane).
 LAS files (read_las, read_las_gen, save_las, append_save_las, pcd2las:
 PointCloudAdvanceIO, las_io.py) are decoded and encoded on the GPU
 (ops.las_unpack / las_pack) and by numpy without one.
+E57 files (read_e57, read_e57_gen, read_e57_scan_gen, read_e57_gen_scan_gen,
+save_e57, save_pcds_e57, e572las: e57_io.py, without pye57) have their page
+checksums verified and their records decoded and encoded on the GPU
+(ops.e57_crc_pages / e57_unpack / e57_pack / e57_seal), by numpy without one.
 Out of scope (SURVEY.md §2
 row 5) and not mirrored: the colour-cosine selections, the reference's
 other cv2 methods (detect_3d_circles, read_single_RGB), compressed LAZ, E57
-(read_e57*, save_e57, e572las), get_lasdata (it returns laspy objects) and the
-image I/O (save_png / save_jpg / save_tiff).
+spherical coordinates and images2D, get_lasdata (it returns laspy objects), the
+E57 scan index of save_las(pt_src_id=True) and the image I/O (save_png /
+save_jpg / save_tiff).
 """
 from __future__ import annotations
 
@@ -40,7 +45,7 @@ from typing import Callable, List, Tuple
 import numpy as np
 import torch
 
-from . import las_io, ops, pcd_io
+from . import e57_io, las_io, ops, pcd_io
 from . import _native as N
 from .params import KDTreeSearchParamKNN, resolve, resolve_estimation
 
@@ -168,7 +173,7 @@ class PointCloudBase:
 
     def __init__(self, xyz=None, rgb=None, normals=None, intensity=None, labels=None, row_index=None,
                  column_index=None, e57=None):
-        self.e57 = None
+        self.e57 = e57          # the E57File of read_e57 (e57_io.E57File)
         self.intensity = []
         self.labels = []
         self.row_index = []
@@ -218,11 +223,15 @@ class PointCloudBase:
         if ok(normals):
             self.set_normals(normals)
         if ok(rgb):
-            rgb = _as_np(rgb)
-            if rgb.max() > 1.0 or rgb.min() < 0.0:   # reference PointCloud.py:36-40
-                rgb = rgb * 1.0
-                rgb = (rgb - rgb.min()) / (rgb.max() - rgb.min())
-            self.set_rgb(rgb)
+            self._set_rgb_rescaled(rgb)
+
+    def _set_rgb_rescaled(self, rgb):
+        """The constructor's colour rule: values outside [0, 1] are min-max rescaled."""
+        rgb = _as_np(rgb)
+        if rgb.max() > 1.0 or rgb.min() < 0.0:   # reference PointCloud.py:36-40
+            rgb = rgb * 1.0
+            rgb = (rgb - rgb.min()) / (rgb.max() - rgb.min())
+        self.set_rgb(rgb)
 
     # ----------------------------------------------------------- storage
     def _copy_from(self, other: "PointCloudBase"):
@@ -898,8 +907,12 @@ class PointCloudAdvanceIO(PointCloudUtility):
     las_io.py holds the format rules; with a GPU the records are decoded and
     encoded by o3dx_las_unpack / o3dx_las_pack, without one by the numpy forms
     of the same rules (identical values).  get_lasdata is not mirrored: it
-    returns laspy objects.  E57 (read_e57*, save_e57, e572las), compressed LAZ
-    and the image I/O are out of scope."""
+    returns laspy objects.  E57 I/O (reference PointCloud.py:569-703) without
+    pye57: e57_io.py holds the format rules and the E57File object; with a GPU
+    the page checksums, the record decode and the encode run in
+    o3dx_e57_crc_pages / o3dx_e57_unpack / o3dx_e57_pack / o3dx_e57_seal,
+    without one in the numpy forms (identical values).  Compressed LAZ, E57
+    spherical coordinates and images2D, and the image I/O are out of scope."""
 
     def get_lasdata(self, *args, **kwargs):
         """Not mirrored: the reference returns a laspy.LasData (PointCloud.py:
@@ -1015,10 +1028,11 @@ class PointCloudAdvanceIO(PointCloudUtility):
         intensity i as int(i * 255) mod 256.  point_format: 0-3 or 6-8.
         OverflowError when a scaled coordinate leaves int32 (as laspy),
         ValueError for non-finite coordinates (this project's rule); in both
-        cases nothing is written.  pt_src_id=True needs the E57 object:
+        cases nothing is written.  pt_src_id=True (the reference's per-scan
+        source id of a stacked E57 cloud) is not mirrored:
         NotImplementedError."""
         if pt_src_id:
-            raise NotImplementedError("save_las(pt_src_id=True) needs the E57 scan index (E57 is not mirrored)")
+            raise NotImplementedError("save_las(pt_src_id=True): the per-scan point source id is not mirrored")
         if point_format not in las_io.WRITABLE:
             raise ValueError(f"save_las: point format {point_format} cannot be written (only {las_io.WRITABLE})")
         sc = np.full(3, 1e-4) if scales is None else np.broadcast_to(np.asarray(scales, np.float64), (3,)).copy()
@@ -1039,7 +1053,7 @@ class PointCloudAdvanceIO(PointCloudUtility):
         file is left as it was."""
         assert os.path.isfile(path), f'file {path} is no exist.'
         if pt_src_id:
-            raise NotImplementedError("append_save_las(pt_src_id=True) needs the E57 scan index (E57 is not mirrored)")
+            raise NotImplementedError("append_save_las(pt_src_id=True): the per-scan point source id is not mirrored")
         h = las_io.read_header(path)
         las_io.check_appendable(h)
         rec, stats = self._las_records(f"append_save_las({path})", h.point_format, h.stride, h.scales, h.offsets, True)
@@ -1054,6 +1068,232 @@ class PointCloudAdvanceIO(PointCloudUtility):
         yield 0.5
         p.save_las(to_path)
         yield 1.0
+
+    # ------------------------------------------------------------------ E57
+    def _e57_open(self, file_path: str, rgb: bool, intensity: bool, row_column: bool):
+        """The cloud's E57File, opened on first use and re-used after (as the
+        reference: PointCloud.py:637-643), with the switches of this call."""
+        if self.e57 is None:
+            self.e57 = e57_io.E57File(file_path, intensity=intensity, colors=rgb, row_column=row_column,
+                                      printinfo=True)
+        else:
+            self.e57.intensity = intensity
+            self.e57.colors = rgb
+            self.e57.row_column = row_column
+            self.e57.point_file = file_path
+        return self.e57
+
+    def _e57_cloud(self, parts, scan_No: int):
+        """A new cloud from decoded E57 records (E57File.decode dicts, stacked)."""
+        c = self.__class__()
+        c.e57 = self.e57
+        c.scan_No = scan_No
+        parts = [d for d in parts if len(d["points32"] if d["device"] else d["points"])]
+        if not parts:
+            return c
+        dev = parts[0]["device"]
+        cat = (lambda a: a[0] if len(a) == 1 else torch.cat(a)) if dev else \
+            (lambda a: a[0] if len(a) == 1 else np.concatenate(a))
+        col = lambda k: None if parts[0][k] is None else cat([d[k] for d in parts])  # noqa: E731
+        rgb, inten, row, column = col("rgb"), col("intensity"), col("row"), col("col")
+        if dev:
+            # the kernel's flag makes _wide known without set_points' passes, as _las_cloud
+            c._pts = cat([d["points32"] for d in parts])
+            c._wide = any(d["wide"] for d in parts)
+            c._pts64 = cat([d["points64"] for d in parts]) if c._wide else None
+            if rgb is not None:
+                # the constructor's rule (reference PointCloud.py:36-40) in float64, on the device
+                r = rgb.double()
+                if float(r.max()) > 1.0:
+                    r = (r - r.min()) / (r.max() - r.min())
+                c._colors = r.float().contiguous()
+            inten, row, column = (None if t is None else t.cpu().numpy() for t in (inten, row, column))
+            if row is not None:
+                row, column = row.view(np.uint16), column.view(np.uint16)
+        else:
+            c.set_points(cat([d["points"] for d in parts]))
+            if rgb is not None:
+                c._set_rgb_rescaled(rgb)
+        if inten is not None:
+            c.set_intensity(np.expand_dims(inten, 1))
+        if row is not None:
+            c.row_index, c.column_index = row, column
+        return c
+
+    def read_e57(self, file_path: str, scan_No: int = -1, rgb: bool = False, intensity: bool = False,
+                 row_column: bool = False, infoOnly: bool = False):
+        """A new cloud from an E57 file (reference PointCloud.py:627-644)
+        without pye57: scan scan_No, or all scans stacked for -1.  As pye57's
+        read_scan, rows whose cartesianInvalidState is not 0 are dropped and
+        the scan's pose transforms the points (R from the quaternion, x' =
+        ((R00 x + R01 y) + R02 z) + t0 in float64: this project's rule).
+        Cartesian coordinates stored as Float single give a float32 cloud;
+        Float double and ScaledInteger scans usually run the float64 kernels
+        (_wide).  rgb: the Integer colours through the constructor's rule
+        (values above 1 are min-max rescaled); intensity: (n,1) float32;
+        row_column: uint16 row_index / column_index.  ValueError when a field
+        asked for is missing.  The result carries .e57 (the E57File) and
+        .scan_No; infoOnly returns an empty cloud with .e57 set.  With a GPU
+        the file's bytes go to the device once: the page checksums and the
+        decode run there.  RuntimeError names the file and the reason for a
+        bad signature, major version or page size, a length that is no
+        multiple of the page size, truncated data, a CRC mismatch (with the
+        first bad page), a stream too short for recordCount and spherical-only
+        scans."""
+        e = self._e57_open(file_path, rgb, intensity, row_column)
+        if infoOnly:
+            c = self.__class__()
+            c.e57 = e
+            return c
+        scans = range(e.scan_count) if scan_No < 0 else [scan_No]
+        return self._e57_cloud([e.decode(i, 0, e.scan_headers[i].point_count, local=False) for i in scans], scan_No)
+
+    def read_e57_gen(self, file_path: str, rgb: bool = False, intensity: bool = False, row_column: bool = False):
+        """read_e57 scan by scan (reference PointCloud.py:646-656)."""
+        e = self._e57_open(file_path, rgb, intensity, row_column)
+        for i in range(e.scan_count):
+            yield self._e57_cloud([e.decode(i, 0, e.scan_headers[i].point_count, local=False)], i)
+
+    def read_e57_scan_gen(self, file_path: str, scan_No: int = 0, rgb: bool = False, intensity: bool = False,
+                          row_column: bool = False, every_k_points: int = 10000000):
+        """One scan in chunks of every_k_points records (reference
+        PointCloud.py:658-671).  The chunks hold the scan's raw local
+        coordinates, unfiltered: no pose, invalid rows kept, as the
+        reference's raw-buffer path yields them.  Exactly ceil(count /
+        every_k_points) chunks: the reference's extra stale chunk at exact
+        multiples is not mirrored."""
+        e = self._e57_open(file_path, rgb, intensity, row_column)
+        for r0, m in e.chunks(scan_No, every_k_points):
+            yield self._e57_cloud([e.decode(scan_No, r0, m, local=True)], scan_No)
+
+    def read_e57_gen_scan_gen(self, file_path: str, rgb: bool = False, intensity: bool = False,
+                              row_column: bool = False, every_k_points: int = 10000000):
+        """read_e57_scan_gen over every scan (reference PointCloud.py:673-687):
+        raw local coordinates, unfiltered, ceil(count / every_k_points) chunks
+        per scan."""
+        e = self._e57_open(file_path, rgb, intensity, row_column)
+        for i in range(e.scan_count):
+            for r0, m in e.chunks(i, every_k_points):
+                yield self._e57_cloud([e.decode(i, r0, m, local=True)], i)
+
+    def _e57_scan(self, normals: bool):
+        """(ScanPlan, XML kinds, columns, bounds, intensity limits) of this
+        cloud as one written scan.  Columns are (tensor, stride, first) on the
+        device, 1-d numpy arrays without one."""
+        S = e57_io
+        n = self.size()
+        gpu = torch.cuda.is_available()
+        fields, kinds, cols = [], [], []
+
+        def add(name, src, bits, kind, col, mn=0, mx=0):
+            fields.append((name, src, bits, mn, mx))
+            kinds.append(kind)
+            cols.append(col)
+
+        def split3(t, names, src, bits, kind):
+            for a, nm in enumerate(names):
+                add(nm, src, bits, kind, (t, 3, a) if gpu else np.ascontiguousarray(t[:, a]))
+
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(_device())  # noqa: E731
+        xyz_names = ("cartesianX", "cartesianY", "cartesianZ")
+        if self._wide:
+            p = self._hot_points() if gpu else self.get_points()
+            split3(p, xyz_names, S.SRC_F64, 64, "double")
+        else:
+            p = self._dev_points() if gpu else self._dev_points().numpy()
+            split3(p, xyz_names, S.SRC_F32, 32, "single")
+        bounds = limits = None
+        if n:
+            lo, hi = (p.amin(0), p.amax(0)) if gpu else (p.min(0), p.max(0))
+            lo, hi = _as_np(lo).astype(np.float64), _as_np(hi).astype(np.float64)
+            bounds = [lo[0], hi[0], lo[1], hi[1], lo[2], hi[2]]
+        if self.has_intensity():
+            i32 = np.asarray(self.get_intensity()).flatten().astype(np.float32)
+            limits = (float(i32.min()), float(i32.max()))
+            add("intensity", S.SRC_F32, 32, "single", (up(i32), 1, 0) if gpu else i32)
+        if self.has_rgb():
+            c = self._colors.to(_device()) if gpu else self._colors.cpu().numpy()
+            split3(c, ("colorRed", "colorGreen", "colorBlue"), S.SRC_COLOUR, 8, (0, 255))
+        if self.has_col_row():
+            column, row = self.get_col_row()
+            for nm, v in (("rowIndex", row), ("columnIndex", column)):
+                v = np.asarray(v).flatten().astype(np.int64)
+                if v.min() < 0:
+                    raise ValueError(f"save_e57: {nm} has negative values")
+                mx = int(v.max())
+                add(nm, S.SRC_I64, mx.bit_length(), (0, mx), (up(v), 1, 0) if gpu else v, 0, mx)
+        if normals and self.has_normals():
+            nr = self._normals.to(_device()) if gpu else self._normals.cpu().numpy()
+            split3(nr, ("nor:normalX", "nor:normalY", "nor:normalZ"), S.SRC_F32, 32, "single")
+        return S.ScanPlan(fields, n), kinds, cols, bounds, limits
+
+    @staticmethod
+    def _e57_write(filename: str, clouds, name, rotation, translation, normals: bool):
+        S = e57_io
+        scans = [c._e57_scan(normals) for c in clouds]
+        plans = [s[0] for s in scans]
+        secs, xml_at = S.layout(plans)
+        parts = [S.scan_xml(p, S.physical(sec), name or f"scan {i}", f"{{{uuid.uuid4()}}}", s[3], s[4], rotation,
+                            translation, s[1]) for i, (p, sec, s) in enumerate(zip(plans, secs, scans))]
+        xml = S.file_xml(parts, any(f[0].startswith("nor:") for p in plans for f in p.fields))
+        size = (xml_at + len(xml) + 3) // 4 * 4
+        head = np.frombuffer(S.file_header(xml_at, len(xml)), np.uint8)
+        gpu = torch.cuda.is_available()
+        image = torch.zeros(size, dtype=torch.uint8, device=_device()) if gpu else np.zeros(size, np.uint8)
+        put = (lambda at, b: image[at:at + len(b)].copy_(torch.from_numpy(np.array(b)))) if gpu else \
+            (lambda at, b: image.__setitem__(slice(at, at + len(b)), b))
+        put(0, head)
+        put(xml_at, np.frombuffer(xml, np.uint8))
+        for p, sec, s in zip(plans, secs, scans):
+            put(sec, np.frombuffer(S.section_header(p, sec), np.uint8))
+            if not p.packets:
+                continue
+            at = sec + S.SECTION_HEADER
+            if gpu:
+                ops.e57_pack(p.tables(), s[2], p.n, p.R, p.full_bytes, p.last_bytes, p.packet_head(False),
+                             p.packet_head(True), out=image[at:at + p.data_bytes])
+            else:
+                image[at:at + p.data_bytes] = S.pack_host(p, s[2])
+        paged = ops.e57_seal(image).cpu().numpy() if gpu else S.seal_host(image)
+        paged.tofile(filename)
+
+    def save_e57(self, filename: str, name: str = None, rotation: np.ndarray = None, translation: np.ndarray = None,
+                 labels: bool = False, normals: bool = True):
+        """Write the cloud as a one-scan E57 file (reference PointCloud.py:
+        614-625) without pye57.  cartesianX/Y/Z are Float double when the
+        cloud holds float64 values float32 cannot (_wide), else Float single;
+        intensity Float single with intensityLimits; colours Integer 0..255,
+        (uint8)(c * 255) as the reference's _get_data_raw_e57; rowIndex /
+        columnIndex Integer 0..max; the stored normals as nor:normalX/Y/Z Float
+        single (normals=False leaves them out).  rotation (quaternion w, x, y,
+        z) / translation are written as the scan's pose: read_e57 applies
+        them.  labels is accepted and unused, as in the reference.  Packets
+        hold a fixed number of records (the largest multiple of 8 that keeps a
+        packet within 65,536 bytes); no index packet is written.  With a GPU
+        the packets and the page checksums are built there."""
+        self._e57_write(filename, [self], name, rotation, translation, normals)
+
+    def save_pcds_e57(self, pcds, filename: str, name: str = None, rotation: np.ndarray = None,
+                      translation: np.ndarray = None, labels: bool = False):
+        """One E57 file with one scan per cloud of pcds (reference
+        PointCloud.py:600-612, which writes this cloud's data once per entry;
+        here every entry's own data), without normals."""
+        self._e57_write(filename, list(pcds), name, rotation, translation, False)
+
+    def e572las(self, from_path: str, to_path: str = None, rgb: bool = False, intensity: bool = False,
+                row_column: bool = False, every_k_points: int = 10000000):
+        """E57 to LAS in chunks (reference PointCloud.py:689-703): a generator
+        of progress fractions; the first chunk goes through save_las, the rest
+        through append_save_las (raw local coordinates, as read_e57_gen_scan_gen
+        yields them)."""
+        if to_path is None:
+            to_path = from_path.replace('.e57', '.las')
+        cnt = 0
+        for i, p in enumerate(self.read_e57_gen_scan_gen(from_path, rgb, intensity, row_column, every_k_points)):
+            p.save_las(to_path) if i == 0 else p.append_save_las(to_path)
+            cnt += p.size()
+            del p
+            yield cnt / self.e57.all_points
 
 
 class PointCloud(PointCloudAdvanceIO):

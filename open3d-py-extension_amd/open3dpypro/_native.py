@@ -176,6 +176,11 @@ _SIGS = {
     # LAS point records (additive to ABI 7)
     "o3dx_las_unpack": (_I32, [_P, _I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "o3dx_las_pack": (_I32, [_P, _I32, _I64, _I64, _I32, _P, _P, _P, _P, _P, _P, _P, _P]),
+    # E57 pages and records (additive to ABI 7)
+    "o3dx_e57_crc_pages": (_I32, [_P, _I64, _P, _P]),
+    "o3dx_e57_unpack": (_I32, [_P, _I64, _I32, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "o3dx_e57_pack": (_I32, [_I32, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
+    "o3dx_e57_seal": (_I32, [_P, _I64, _P, _I64, _P]),
 }
 
 _lib = None

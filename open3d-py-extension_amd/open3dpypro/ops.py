@@ -618,6 +618,127 @@ def las_pack(xyz: torch.Tensor, stride: int, point_format: int, scales, offsets,
     return rec, stats
 
 
+def _e57_bytes(t: torch.Tensor, what: str) -> torch.Tensor:
+    N.require_device(t, what)
+    if t.dtype != torch.uint8 or t.ndim != 1:
+        raise RuntimeError(f"{what} must be a 1-d uint8 tensor, got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def e57_crc_pages(file_bytes: torch.Tensor):
+    """CRC32C of every whole 1024-byte page of an E57 file's bytes against its
+    big-endian trailer, on the device (o3dx_e57_crc_pages).  Returns (bad
+    pages, first bad page or -1) as Python ints (waits)."""
+    f = _e57_bytes(file_bytes, "file_bytes")
+    out = torch.empty(2, dtype=torch.int64, device=f.device)
+    N.check(N.load().o3dx_e57_crc_pages(N.ptr(f), f.numel() // 1024, N.ptr(out), N.stream_ptr(f.device)),
+            "e57_crc_pages")
+    bad, first = out.cpu().tolist()
+    return int(bad), int(first) if bad else -1
+
+
+def e57_unpack(file_bytes: torch.Tensor, desc, affine, segments, r0: int, n: int, pose=None):
+    """Records [r0, r0 + n) of one E57 scan decoded on the device from the
+    paged file bytes (o3dx_e57_unpack; include/o3dx.h states the rules).
+    desc (k,6) int64 {role, kind, bits, minimum, first segment row, segment
+    rows}, affine (k,2) float64 {scale, offset}, segments (m,3) int64 {stream
+    byte offset, logical file offset, length} (e57_io.field_tables); pose: 12
+    float64 (R row-major, t) or None.  Returns device tensors for the roles
+    present: points64 / points32 (n,3), rgb (n,3) uint8, intensity (n,)
+    float32, row / col (n,) int16 holding the u16 bits, invalid (n,) int8
+    (None otherwise), and flags (1,) int32 (bit 0: some coordinate is not a
+    float32 value; bit 1: a record's bytes lie outside its segments or the
+    file).  No host wait: reading flags is the caller's."""
+    f = _e57_bytes(file_bytes, "file_bytes")
+    dev = f.device
+    d = _c(desc, np.int64).reshape(-1, 6)
+    a = _c(affine, np.float64).reshape(-1, 2)
+    sg = _c(segments, np.int64).reshape(-1, 3)
+    if len(a) != len(d):
+        raise RuntimeError(f"affine must have one row per field ({len(d)}), got {len(a)}")
+    r0, n = int(r0), int(n)
+    if n < 0:
+        raise RuntimeError(f"n must be >= 0, got {n}")
+    seg = torch.from_numpy(sg).to(dev) if len(sg) else None
+    roles = set(int(r) for r in d[:, 0])
+    xyz = {0, 1, 2} <= roles
+    new = lambda ok, shape, dt: torch.empty(shape, dtype=dt, device=dev) if ok else None  # noqa: E731
+    p64, p32 = new(xyz, (n, 3), torch.float64), new(xyz, (n, 3), torch.float32)
+    col = new({4, 5, 6} <= roles, (n, 3), torch.uint8)
+    inten = new(3 in roles, (n,), torch.float32)
+    row, cl = new(7 in roles, (n,), torch.int16), new(8 in roles, (n,), torch.int16)
+    inv = new(9 in roles, (n,), torch.int8)
+    flags = torch.empty(1, dtype=torch.int32, device=dev)
+    ps = None if pose is None else _c(pose, np.float64).reshape(12)
+    N.check(N.load().o3dx_e57_unpack(N.ptr(f), f.numel(), len(d), _np_ptr(d), _np_ptr(a), N.ptr(seg), len(sg), r0, n,
+                                     _np_ptr(ps), N.ptr(p64), N.ptr(p32), N.ptr(col), N.ptr(inten), N.ptr(row),
+                                     N.ptr(cl), N.ptr(inv), N.ptr(flags), N.stream_ptr(dev)), "e57_unpack")
+    return {"points64": p64, "points32": p32, "rgb": col, "intensity": inten, "row": row, "col": cl, "invalid": inv,
+            "flags": flags}
+
+
+def e57_pack(desc, sources, n: int, records_per_packet: int, full_bytes: int, last_bytes: int, head_full: bytes,
+             head_last: bytes, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One E57 scan's data packets, headers included, encoded on the device
+    (o3dx_e57_pack).  desc (k,6) int64 {source kind, bits, minimum, stream
+    offset in a full packet, in the last packet, stream bytes in the last
+    packet} and the packet geometry come from e57_io.ScanPlan; sources: per
+    field (tensor, element stride, first element) — float32, float64 or int64
+    device tensors as the source kind says.  Returns the packets as a uint8
+    tensor ((packets - 1) * full_bytes + last_bytes bytes; `out`, a 4-byte
+    aligned uint8 tensor of that size, is filled when given).  Not waited for."""
+    d = _c(desc, np.int64).reshape(-1, 6)
+    n, R = int(n), int(records_per_packet)
+    if len(sources) != len(d) or not len(d):
+        raise RuntimeError(f"sources must have one entry per field ({len(d)}), got {len(sources)}")
+    want = {0: torch.float32, 1: torch.float64, 2: torch.float32, 3: torch.int64}
+    keep, ptrs, strides = [], [], np.zeros((len(d), 2), np.int64)
+    dev = None
+    for k, (t, stride, first) in enumerate(sources):
+        N.require_device(t, f"source {k}")
+        if t.dtype != want.get(int(d[k, 0])):
+            raise RuntimeError(f"source {k} must be {want.get(int(d[k, 0]))} for source kind {int(d[k, 0])}, got "
+                               f"{t.dtype}")
+        t = t.contiguous()
+        if n and (int(first) < 0 or int(stride) < 0 or int(first) + (n - 1) * int(stride) >= t.numel()):
+            raise RuntimeError(f"source {k}: {n} records at stride {stride} from element {first} leave its "
+                               f"{t.numel()} elements")
+        keep.append(t)
+        ptrs.append(t.data_ptr())
+        strides[k] = (int(stride), int(first))
+        dev = t.device
+    packets = (n + R - 1) // R if R > 0 else 0
+    size = (packets - 1) * int(full_bytes) + int(last_bytes) if packets else 0
+    if out is None:
+        out = torch.empty(size, dtype=torch.uint8, device=dev)
+    else:
+        N.require_device(out, "out")
+        if out.dtype != torch.uint8 or out.numel() != size or not out.is_contiguous():
+            raise RuntimeError(f"out must be a contiguous uint8 tensor of {size} bytes")
+    arr = (ctypes.c_void_p * len(d))(*ptrs)
+    hf, hl = _c(np.frombuffer(bytes(head_full), np.uint8), np.uint8), _c(np.frombuffer(bytes(head_last), np.uint8),
+                                                                         np.uint8)
+    if len(hf) != 6 + 2 * len(d) or len(hl) != len(hf):
+        raise RuntimeError(f"packet headers must be {6 + 2 * len(d)} bytes, got {len(hf)} and {len(hl)}")
+    N.check(N.load().o3dx_e57_pack(len(d), _np_ptr(d), ctypes.cast(arr, ctypes.c_void_p), _np_ptr(strides), n, R,
+                                   int(full_bytes), int(last_bytes), _np_ptr(hf), _np_ptr(hl), N.ptr(out),
+                                   N.stream_ptr(dev)), "e57_pack")
+    del keep
+    return out
+
+
+def e57_seal(logical_bytes: torch.Tensor) -> torch.Tensor:
+    """Logical bytes laid into 1024-byte E57 pages, each with its CRC32C
+    trailer, on the device (o3dx_e57_seal); the last page is zero-padded."""
+    lg = _e57_bytes(logical_bytes, "logical_bytes")
+    if lg.numel() % 4:
+        lg = torch.cat([lg, torch.zeros(4 - lg.numel() % 4, dtype=torch.uint8, device=lg.device)])
+    pages = (lg.numel() + 1019) // 1020
+    out = torch.empty(pages * 1024, dtype=torch.uint8, device=lg.device)
+    N.check(N.load().o3dx_e57_seal(N.ptr(lg), lg.numel(), N.ptr(out), pages, N.stream_ptr(lg.device)), "e57_seal")
+    return out
+
+
 def ransac_samples(n: int, ransac_n: int, num_iterations: int, seed: int) -> np.ndarray:
     """Open3D RandomSampler over mt19937(seed): (iters, ransac_n) int32."""
     out = np.empty((max(num_iterations, 1), ransac_n), np.int32)
