@@ -1108,6 +1108,59 @@ int o3dx_e57_pack(int n_fields, const int64_t* desc_host, const void* const* src
 int o3dx_e57_seal(const uint8_t* logical_dev, int64_t logical_bytes, uint8_t* paged_out_dev, int64_t n_pages,
                   void* stream);
 
+/* ------------------------------------- global registration (additive to ABI 7)
+ * Open3D's compute_fpfh_feature and registration_ransac_based_on_feature_matching
+ * / _on_correspondence.  The semantics are Open3D's as restated in DESIGN.md
+ * §4.11 (tests/globalreg_oracle.py is the executable form the tests pin).
+ *
+ * o3dx_fpfh: the (n,33) float32 FPFH of points with normals.  The neighbour
+ *   lists are o3dx_knn_search(xyz, xyz, mode, knn, radius) — sorted by (d^2,
+ *   index), the point itself included — taken once; mode KNN or HYBRID, knn
+ *   <= O3DX_MAX_KNN (RADIUS: O3DX_ENOTSUP, unbounded lists).  All arithmetic
+ *   float64 on the float32 inputs, rounded once to float32.  Pass 1 writes one
+ *   36-byte SPFH row per point: the 33 integer bin counts (each <= 63), byte
+ *   33 the list length m, bytes 34..35 zero; SPFH bin b = count_b * 100 / (m -
+ *   1).  Pass 2 gathers the neighbours' rows.  spfh_out_dev (nullable, n x 36
+ *   bytes) receives the rows.  Integer and fixed-order accumulation only: two
+ *   runs give the same bits.
+ * o3dx_feature_match: for each of ns source rows (33 float32) the target row
+ *   (of nt >= 1) with the smallest squared distance, (a - b)^2 summed over the
+ *   33 components in float32, component order; the lowest target index wins a
+ *   tie.  idx_out_dev (ns) int32, d2_out_dev (nullable, ns) float32.
+ * o3dx_umeyama_from_samples: host only.  coords_host (H x ransac_n x 2 x 3
+ *   float64: the sampled source point, then its target point) -> T_host (H x
+ *   16): TransformationEstimationPointToPoint(false) of each sample through
+ *   o3dx_icp_solve_point_to_point (the identity for a rank-deficient sample).
+ * o3dx_corr_check: host only.  pass_host[h] = 1 when sample h passes
+ *   CorrespondenceCheckerBasedOnEdgeLength(edge_similarity) (skipped when
+ *   edge_similarity < 0: fails if for any two sampled pairs |pi - pj| < |qi -
+ *   qj| s or |qi - qj| < |pi - pj| s) and CorrespondenceCheckerBasedOnDistance
+ *   (distance_threshold) (skipped when < 0: fails if any |T p - q| > t).
+ * o3dx_corr_count: counts_host[h] = the exact number of correspondences
+ *   (corr_dev: C x 2 int32, source and target index) with |T_h p - q| <
+ *   max_distance.  float32 distance with a guard band around the threshold,
+ *   inside which the decision is made again in float64 in the pinned order:
+ *   T p = ((T0 x + T1 y) + T2 z) + T3 per row, d = sqrt((dx^2 + dy^2) + dz^2),
+ *   strict <.  Integer ballots.
+ * o3dx_corr_error2: sums_host[h] = sum of d * d over those inliers, float64 in
+ *   a fixed order (counts_host nullable: the counts again). */
+size_t o3dx_fpfh_workspace_bytes(int64_t n, int knn);
+int o3dx_fpfh(const float* xyz_dev, const float* normals_dev, int64_t n, int mode, int knn, double radius,
+              float* out_dev, uint8_t* spfh_out_dev, void* ws, size_t ws_bytes, void* stream);
+size_t o3dx_feature_match_workspace_bytes(int64_t ns, int64_t nt);
+int o3dx_feature_match(const float* src_feat_dev, int64_t ns, const float* tgt_feat_dev, int64_t nt,
+                       int32_t* idx_out_dev, float* d2_out_dev, void* ws, size_t ws_bytes, void* stream);
+int o3dx_umeyama_from_samples(const double* coords_host, int num_hypotheses, int ransac_n, double* T_host);
+int o3dx_corr_check(const double* coords_host, int num_hypotheses, int ransac_n, const double* T_host,
+                    double edge_similarity, double distance_threshold, uint8_t* pass_host);
+size_t o3dx_corr_count_workspace_bytes(int64_t c, int num_hypotheses);
+int o3dx_corr_count(const float* src_dev, const float* tgt_dev, const int32_t* corr_dev, int64_t c,
+                    const double* T_host, int num_hypotheses, double max_distance, int64_t* counts_host,
+                    void* ws, size_t ws_bytes, void* stream);
+int o3dx_corr_error2(const float* src_dev, const float* tgt_dev, const int32_t* corr_dev, int64_t c,
+                     const double* T_host, int num_hypotheses, double max_distance, double* sums_host,
+                     int64_t* counts_host, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -47,7 +47,8 @@ import torch
 
 from . import e57_io, las_io, ops, pcd_io
 from . import _native as N
-from .params import KDTreeSearchParamKNN, resolve, resolve_estimation
+from .params import (Feature, KDTreeSearchParamHybrid, KDTreeSearchParamKNN, RANSACConvergenceCriteria,
+                     TransformationEstimationPointToPoint, resolve, resolve_checkers, resolve_estimation)
 
 _SEED = [None]
 
@@ -1562,3 +1563,88 @@ class PointCloud(PointCloudAdvanceIO):
                                  estimation=est, with_scaling=with_scaling)
         return RegistrationResult(r["transformation"], r["fitness"], r["inlier_rmse"],
                                   r["correspondence_set"].cpu().numpy().astype(np.int64))
+
+    # ------------------------------------------------- global registration
+    def evaluate_registration(self, target: "PointCloudBase", max_correspondence_distance: float,
+                              transformation=None):
+        """Open3D evaluate_registration: fitness, inlier_rmse and the
+        correspondences (every source point's nearest target point within the
+        distance) under `transformation` — registration_icp at max_iteration=0."""
+        return self.registration_icp(target, max_correspondence_distance, init=transformation, max_iteration=0,
+                                     estimation="point_to_point")
+
+    def compute_fpfh_feature(self, param=KDTreeSearchParamHybrid(0.1, 64)):
+        """Open3D compute_fpfh_feature on the GPU -> params.Feature (.data (33,
+        N) float64; the device rows are kept for the matcher).  The neighbour
+        lists are this library's (sorted by (d^2, index), strict d^2 < r^2, the
+        point itself included).  KNN(k) or Hybrid(radius, max_nn) with k,
+        max_nn <= 64 (ValueError above); Radius raises NotImplementedError
+        (unbounded lists); RuntimeError without normals, as Open3D; float64
+        clouds that float32 cannot hold raise NotImplementedError."""
+        mode, knn, radius = resolve(param)
+        if mode == N.SEARCH_RADIUS:
+            raise NotImplementedError("compute_fpfh_feature: KDTreeSearchParamRadius has unbounded neighbour lists; "
+                                      "use KDTreeSearchParamHybrid(radius, max_nn <= 64) or KDTreeSearchParamKNN")
+        if knn > N.MAX_KNN or knn < 1:
+            raise ValueError(f"compute_fpfh_feature: knn / max_nn must be in 1..{N.MAX_KNN} (O3DX_MAX_KNN), got {knn}")
+        if not self.has_normals():
+            raise RuntimeError("Failed because input point cloud has no normal.")
+        if self._wide:
+            raise NotImplementedError("float64 clouds that float32 cannot hold are outside compute_fpfh_feature "
+                                      "(pass float32 values)")
+        return Feature(dev=ops.fpfh(self._dev_points(), self._normals, mode=mode, knn=knn, radius=radius))
+
+    def _ransac_args(self, target, estimation, checkers, criteria, what):
+        est, with_scaling = resolve_estimation(estimation)
+        if est != "point_to_point" or with_scaling:
+            raise ValueError(f"{what}: only TransformationEstimationPointToPoint(with_scaling=False) is supported")
+        edge, dist = resolve_checkers(checkers)
+        if self._wide or target._wide:
+            raise NotImplementedError(f"float64 clouds that float32 cannot hold are outside {what} "
+                                      "(pass float32 values)")
+        return edge, dist, int(criteria.max_iteration), float(criteria.confidence)
+
+    def registration_ransac_based_on_correspondence(self, target: "PointCloudBase", corres,
+                                                    max_correspondence_distance: float,
+                                                    estimation=TransformationEstimationPointToPoint(False),
+                                                    ransac_n: int = 3, checkers=[],
+                                                    criteria=RANSACConvergenceCriteria(100000, 0.999), seed=None):
+        """Open3D registration_ransac_based_on_correspondence on the GPU
+        (ops.registration_ransac_based_on_correspondence states the rule).
+        corres: (C, 2) source / target indices.  The samples are
+        ops.ransac_samples(C, ransac_n, max_iteration, seed) — distinct within
+        a sample and seeded, where Open3D draws with replacement from an
+        unseeded generator; seed=None takes the package's
+        seed sequence (set_random_seed).  The result is the winning
+        transformation evaluated over every source point, as Open3D returns
+        it.  ransac_n < 3, fewer than ransac_n correspondences or a distance
+        <= 0 give the empty result; ValueError for another estimation or the
+        normal checker."""
+        edge, dist, max_it, conf = self._ransac_args(target, estimation, checkers, criteria,
+                                                     "registration_ransac_based_on_correspondence")
+        c = corres if isinstance(corres, torch.Tensor) else np.asarray(corres).reshape(-1, 2)
+        if ransac_n < 3 or len(c) < ransac_n or max_correspondence_distance <= 0.0:
+            return RegistrationResult(np.eye(4), 0.0, 0.0, np.zeros((0, 2), np.int64))
+        r = ops.registration_ransac_based_on_correspondence(
+            self._dev_points(), target._dev_points(), c, max_correspondence_distance, ransac_n, edge, dist, max_it,
+            conf, seed=_next_seed() if seed is None else seed)
+        return self.evaluate_registration(target, max_correspondence_distance, r["transformation"])
+
+    def registration_ransac_based_on_feature_matching(self, target: "PointCloudBase", source_feature, target_feature,
+                                                      mutual_filter: bool, max_correspondence_distance: float,
+                                                      estimation=TransformationEstimationPointToPoint(False),
+                                                      ransac_n: int = 3, checkers=[],
+                                                      criteria=RANSACConvergenceCriteria(100000, 0.999), seed=None):
+        """Open3D registration_ransac_based_on_feature_matching on the GPU:
+        the correspondences of ops.correspondences_from_features(source_feature,
+        target_feature, mutual_filter), then
+        registration_ransac_based_on_correspondence."""
+        self._ransac_args(target, estimation, checkers, criteria, "registration_ransac_based_on_feature_matching")
+        if ransac_n < 3 or max_correspondence_distance <= 0.0:
+            return RegistrationResult(np.eye(4), 0.0, 0.0, np.zeros((0, 2), np.int64))
+        if source_feature.num() != self.size() or target_feature.num() != target.size():
+            raise RuntimeError("registration_ransac_based_on_feature_matching: one feature column per point")
+        corres = ops.correspondences_from_features(source_feature.device_rows(), target_feature.device_rows(),
+                                                   mutual_filter)
+        return self.registration_ransac_based_on_correspondence(target, corres, max_correspondence_distance,
+                                                                estimation, ransac_n, checkers, criteria, seed)

@@ -8,6 +8,8 @@ runs in libo3dx.so (hand-written HIP for gfx950); Open3D is not required.
 from . import _native, ops, synthetic  # noqa: F401
 from .params import KDTreeSearchParamHybrid, KDTreeSearchParamKNN, KDTreeSearchParamRadius  # noqa: F401
 from .params import TransformationEstimationPointToPlane, TransformationEstimationPointToPoint  # noqa: F401
+from .params import (CorrespondenceCheckerBasedOnDistance, CorrespondenceCheckerBasedOnEdgeLength,  # noqa: F401
+                     Feature, RANSACConvergenceCriteria)
 from .PointCloud import (KDTreeGrid, PointCloud, PointCloudAdvanceIO, PointCloudBase,  # noqa: F401
                          PointCloudSelections, PointCloudUtility, RegistrationResult, set_random_seed)
 from .PointCloudMat import *  # noqa: F401,F403

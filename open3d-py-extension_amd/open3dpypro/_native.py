@@ -181,6 +181,16 @@ _SIGS = {
     "o3dx_e57_unpack": (_I32, [_P, _I64, _I32, _P, _P, _P, _I64, _I64, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "o3dx_e57_pack": (_I32, [_I32, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P, _P, _P]),
     "o3dx_e57_seal": (_I32, [_P, _I64, _P, _I64, _P]),
+    # FPFH, feature matching, RANSAC on correspondences (additive to ABI 7)
+    "o3dx_fpfh_workspace_bytes": (_SZ, [_I64, _I32]),
+    "o3dx_fpfh": (_I32, [_P, _P, _I64, _I32, _I32, _D, _P, _P, _P, _SZ, _P]),
+    "o3dx_feature_match_workspace_bytes": (_SZ, [_I64, _I64]),
+    "o3dx_feature_match": (_I32, [_P, _I64, _P, _I64, _P, _P, _P, _SZ, _P]),
+    "o3dx_umeyama_from_samples": (_I32, [_P, _I32, _I32, _P]),
+    "o3dx_corr_check": (_I32, [_P, _I32, _I32, _P, _D, _D, _P]),
+    "o3dx_corr_count_workspace_bytes": (_SZ, [_I64, _I32]),
+    "o3dx_corr_count": (_I32, [_P, _P, _P, _I64, _P, _I32, _D, _P, _P, _SZ, _P]),
+    "o3dx_corr_error2": (_I32, [_P, _P, _P, _I64, _P, _I32, _D, _P, _P, _P, _SZ, _P]),
 }
 
 _lib = None

@@ -1270,4 +1270,334 @@ def registration_icp(src: torch.Tensor, tgt: torch.Tensor, tgt_normals: Optional
     return out
 
 
+def evaluate_registration(src: torch.Tensor, tgt: torch.Tensor, max_correspondence_distance: float, transformation=None):
+    """Open3D evaluate_registration (GetRegistrationResultAndCorrespondences):
+    every source point's nearest target point within the distance under the
+    given transformation — registration_icp's step at max_iteration = 0."""
+    return registration_icp(src, tgt, None, max_correspondence_distance, init=transformation, max_iteration=0,
+                            estimation="point_to_point")
+
+
+# ------------------------------------------------ FPFH, matching, RANSAC on correspondences
+FPFH_DIM = 33
+_SPFH_ROW = 36
+
+
+def fpfh(xyz: torch.Tensor, normals: torch.Tensor, mode: int = N.SEARCH_HYBRID, knn: int = 100, radius: float = 0.0,
+         return_spfh: bool = False):
+    """Open3D compute_fpfh_feature: (n, 33) float32 on the device (o3dx_fpfh;
+    the neighbour lists are knn_search(xyz, xyz, mode, knn, radius)).  With
+    return_spfh also the integer SPFH bin counts (n, 33) uint8 and the list
+    lengths (n,) uint8.  ValueError for knn / max_nn above MAX_KNN,
+    NotImplementedError for a radius search (unbounded lists)."""
+    if int(mode) == N.SEARCH_RADIUS:
+        raise NotImplementedError("fpfh: a radius search has unbounded neighbour lists; use KNN or Hybrid")
+    if int(mode) not in (N.SEARCH_KNN, N.SEARCH_HYBRID):
+        raise ValueError(f"fpfh: unknown search mode {mode}")
+    if int(knn) > N.MAX_KNN or int(knn) < 1:
+        raise ValueError(f"fpfh: knn / max_nn must be in 1..{N.MAX_KNN} (O3DX_MAX_KNN), got {knn}")
+    if _is64(xyz):
+        raise NotImplementedError("float64 points are outside fpfh (pass float32 values)")
+    x = _xyz(xyz)
+    nr = _xyz(normals.to(x.device), "normals")
+    n = x.shape[0]
+    if nr.shape[0] != n:
+        raise RuntimeError(f"fpfh: {n} points but {nr.shape[0]} normals")
+    L = N.load()
+    dev = x.device
+    out = torch.zeros((n, FPFH_DIM), dtype=torch.float32, device=dev)
+    rows = torch.zeros((n, _SPFH_ROW), dtype=torch.uint8, device=dev) if return_spfh else None
+    if n > 0:
+        ws = N.workspace(L.o3dx_fpfh_workspace_bytes(n, int(knn)), dev)
+        N.check(L.o3dx_fpfh(N.ptr(x), N.ptr(nr), n, int(mode), int(knn), float(radius), N.ptr(out), N.ptr(rows),
+                            N.ptr(ws), ws.numel(), N.stream_ptr(dev)), "fpfh")
+    if return_spfh:
+        return out, rows[:, :FPFH_DIM], rows[:, FPFH_DIM]
+    return out
+
+
+def _feat(t: torch.Tensor, what: str) -> torch.Tensor:
+    N.require_device(t, what)
+    if t.ndim != 2 or t.shape[1] != FPFH_DIM:
+        raise RuntimeError(f"{what} must have shape (n, {FPFH_DIM}), got {tuple(t.shape)}")
+    return t.float().contiguous()
+
+
+def feature_match(src_feat: torch.Tensor, tgt_feat: torch.Tensor, return_d2: bool = False):
+    """For each source row (33 float32) the nearest target row's index (ns,)
+    int32, the lowest index on a tie (o3dx_feature_match)."""
+    a = _feat(src_feat, "source features")
+    b = _feat(tgt_feat.to(a.device), "target features")
+    ns, nt = a.shape[0], b.shape[0]
+    dev = a.device
+    idx = torch.empty(ns, dtype=torch.int32, device=dev)
+    d2 = torch.empty(ns, dtype=torch.float32, device=dev) if return_d2 else None
+    if ns > 0:
+        if nt == 0:
+            raise RuntimeError("feature_match: no target features")
+        L = N.load()
+        ws = N.workspace(L.o3dx_feature_match_workspace_bytes(ns, nt), dev)
+        N.check(L.o3dx_feature_match(N.ptr(a), ns, N.ptr(b), nt, N.ptr(idx), N.ptr(d2), N.ptr(ws), ws.numel(),
+                                     N.stream_ptr(dev)), "feature_match")
+    return (idx, d2) if return_d2 else idx
+
+
+def correspondences_from_features(src_feat: torch.Tensor, tgt_feat: torch.Tensor, mutual_filter: bool = False,
+                                  mutual_consistency_ratio: float = 0.1) -> torch.Tensor:
+    """Open3D CorrespondencesFromFeatures: (C, 2) int32 on the device,
+    ascending in the source index — the forward pairs (i, j(i)); with
+    mutual_filter those with i(j(i)) == i, unless fewer than
+    mutual_consistency_ratio * ns of them are mutual (then the forward pairs)."""
+    a = _feat(src_feat, "source features")
+    b = _feat(tgt_feat.to(a.device), "target features")
+    ns, nt = a.shape[0], b.shape[0]
+    if ns == 0 or nt == 0:
+        return torch.zeros((0, 2), dtype=torch.int32, device=a.device)
+    fwd = feature_match(a, b)
+    i = torch.arange(ns, dtype=torch.int32, device=a.device)
+    pairs = torch.stack([i, fwd], dim=1)
+    if not mutual_filter:
+        return pairs
+    back = feature_match(b, a)
+    keep = back[fwd.long()] == i
+    mutual = pairs[keep]
+    if mutual.shape[0] < float(mutual_consistency_ratio) * ns:
+        return pairs
+    return mutual.contiguous()
+
+
+def umeyama_from_samples(coords: np.ndarray) -> np.ndarray:
+    """TransformationEstimationPointToPoint(False) of H samples at once, host
+    only: coords (H, ransac_n, 2, 3) float64 (source point, target point) ->
+    (H, 4, 4); the identity for a rank-deficient sample."""
+    c = _c(coords, np.float64)
+    if c.ndim != 4 or c.shape[2:] != (2, 3) or c.shape[1] < 1:
+        raise RuntimeError(f"umeyama_from_samples: coords must be (H, ransac_n, 2, 3), got {c.shape}")
+    H, rn = c.shape[0], c.shape[1]
+    T = np.zeros((max(H, 1), 4, 4), np.float64)
+    N.check(N.load().o3dx_umeyama_from_samples(_np_ptr(c), H, rn, _np_ptr(T)), "umeyama_from_samples")
+    return T[:H]
+
+
+def corr_check(coords: np.ndarray, T: np.ndarray, edge_similarity: float = -1.0,
+               distance_threshold: float = -1.0) -> np.ndarray:
+    """Open3D's correspondence checkers on H samples, host only (bool (H,)):
+    EdgeLength(edge_similarity) and Distance(distance_threshold), each
+    skipped when negative."""
+    c = _c(coords, np.float64)
+    H, rn = c.shape[0], c.shape[1]
+    TT = _c(T, np.float64).reshape(-1, 4, 4)
+    if TT.shape[0] != H:
+        raise RuntimeError("corr_check: one transformation per sample")
+    out = np.zeros(max(H, 1), np.uint8)
+    N.check(N.load().o3dx_corr_check(_np_ptr(c), H, rn, _np_ptr(TT), float(edge_similarity),
+                                     float(distance_threshold), _np_ptr(out)), "corr_check")
+    return out[:H].astype(bool)
+
+
+def _corr_inputs(src, tgt, corres):
+    s = _xyz(src, "source points")
+    t = _xyz(tgt.to(s.device), "target points")
+    c = corres if isinstance(corres, torch.Tensor) else torch.as_tensor(np.asarray(corres).reshape(-1, 2))
+    c = c.to(device=s.device, dtype=torch.int32).contiguous()
+    if c.ndim != 2 or c.shape[1] != 2:
+        raise RuntimeError(f"correspondences must have shape (C, 2), got {tuple(c.shape)}")
+    if c.shape[0] > 0:
+        lo = int(c.min().item())
+        hi0, hi1 = int(c[:, 0].max().item()), int(c[:, 1].max().item())
+        if lo < 0 or hi0 >= s.shape[0] or hi1 >= t.shape[0]:
+            raise RuntimeError("correspondences: an index is out of range")
+    return s, t, c
+
+
+def _corr_call(name, src, tgt, corres, T, max_distance, want_sums):
+    s, t, c = _corr_inputs(src, tgt, corres)
+    TT = _c(T, np.float64).reshape(-1, 4, 4)
+    H, C = TT.shape[0], c.shape[0]
+    L = N.load()
+    counts = np.zeros(max(H, 1), np.int64)
+    ws = N.workspace(L.o3dx_corr_count_workspace_bytes(C, H), s.device)
+    if want_sums:
+        sums = np.zeros(max(H, 1), np.float64)
+        N.check(L.o3dx_corr_error2(N.ptr(s), N.ptr(t), N.ptr(c), C, _np_ptr(TT), H, float(max_distance),
+                                   _np_ptr(sums), _np_ptr(counts), N.ptr(ws), ws.numel(), N.stream_ptr(s.device)),
+                name)
+        return sums[:H], counts[:H]
+    N.check(L.o3dx_corr_count(N.ptr(s), N.ptr(t), N.ptr(c), C, _np_ptr(TT), H, float(max_distance),
+                              _np_ptr(counts), N.ptr(ws), ws.numel(), N.stream_ptr(s.device)), name)
+    return counts[:H]
+
+
+def corr_count(src, tgt, corres, T, max_distance: float) -> np.ndarray:
+    """Exact inlier counts (H,) int64 of the transformations T (H, 4, 4)
+    over the correspondences: |T p - q| < max_distance (o3dx_corr_count)."""
+    return _corr_call("corr_count", src, tgt, corres, T, max_distance, False)
+
+
+def corr_error2(src, tgt, corres, T, max_distance: float, return_counts: bool = False):
+    """Sum of d^2 over the inliers of each transformation, fixed-order float64
+    (o3dx_corr_error2)."""
+    sums, counts = _corr_call("corr_error2", src, tgt, corres, T, max_distance, True)
+    return (sums, counts) if return_counts else sums
+
+
+def ransac_est_k(fitness: float, ransac_n: int, confidence: float) -> float:
+    """Open3D's iteration estimate log(1 - confidence) / log(1 - fitness^n);
+    0 at fitness 1, +inf where the denominator rounds to 0."""
+    if fitness >= 1.0:
+        return 0.0
+    den = np.log(1.0 - fitness ** ransac_n)
+    if den == 0.0:
+        return float("inf")
+    return float(np.log(1.0 - confidence) / den)
+
+
+class CorrRansacReplay:
+    """Open3D's sequential selection rule of RegistrationRANSACBasedOnCorrespondence
+    over scored hypotheses, fed in iteration order: better = larger fitness,
+    or equal fitness with a smaller rmse; an improvement lowers est_k.  The
+    counts alone decide est_k (an rmse improvement leaves the fitness as it
+    is), so `consults` can name beforehand the hypotheses whose sum d^2 the
+    rule needs."""
+
+    def __init__(self, C: int, ransac_n: int, max_iteration: int, confidence: float):
+        self.C, self.rn, self.conf = int(C), int(ransac_n), float(confidence)
+        self.max_iteration = int(max_iteration)
+        self.est_k = float(max_iteration)
+        self.best_count = 0
+        self.best_err2 = None  # sum d^2 of the best (None: not needed yet)
+        self.best_itr = -1
+        self.best_T = np.eye(4)
+        self.floor = 0  # the iteration after the last one that lowered est_k
+
+    def stopped(self, itr: int) -> bool:
+        return itr >= self.est_k
+
+    def processed(self) -> int:
+        """Iterations the loop runs before est_k stops it: the first itr >=
+        est_k, which cannot precede the iteration after the one that set it."""
+        if self.est_k >= self.max_iteration:
+            return self.max_iteration
+        return int(min(self.max_iteration, max(self.floor, np.ceil(self.est_k))))
+
+    def consults(self, itrs, counts):
+        """Positions in (itrs, counts) whose sum d^2 the rule consults when it
+        is fed them in order (ties with the running best), and whether the
+        incoming best's own sum is consulted."""
+        est_k, bc = self.est_k, self.best_count
+        need, need_best, cur = [], False, -1  # cur: position of the running best in this batch
+        for p, (itr, c) in enumerate(zip(itrs, counts)):
+            if itr >= est_k:
+                break
+            c = int(c)
+            if c > bc:
+                bc, cur = c, p
+                est_k = min(est_k, ransac_est_k(c / self.C, self.rn, self.conf))
+            elif c == bc and c > 0:
+                need.append(p)
+                if cur >= 0:
+                    need.append(cur)
+                else:
+                    need_best = True
+        return sorted(set(need)), need_best
+
+    def feed(self, itr: int, count: int, T, err2=None) -> bool:
+        """One scored hypothesis; err2 (sum d^2) is required on a tie.  False
+        once est_k has stopped the loop."""
+        if itr >= self.est_k:
+            return False
+        count = int(count)
+        better = count > self.best_count
+        if not better and count == self.best_count and count > 0:
+            # equal fitness: rmse = sqrt(err2 / count), the same count on both sides
+            better = np.sqrt(err2 / count) < np.sqrt(self.best_err2 / count)
+        if better:
+            self.best_count, self.best_err2, self.best_itr = count, err2, int(itr)
+            self.best_T = np.array(T, np.float64).reshape(4, 4)
+            k = ransac_est_k(count / self.C, self.rn, self.conf)
+            if k < self.est_k:
+                self.est_k, self.floor = k, int(itr) + 1
+        return True
+
+
+def registration_ransac_based_on_correspondence(src: torch.Tensor, tgt: torch.Tensor, corres,
+                                                max_correspondence_distance: float, ransac_n: int = 3,
+                                                edge_similarity: float = -1.0, distance_threshold: float = -1.0,
+                                                max_iteration: int = 100000, confidence: float = 0.999,
+                                                samples: Optional[np.ndarray] = None, seed: int = 0,
+                                                round_size: int = 4096):
+    """Open3D RegistrationRANSACBasedOnCorrespondence with
+    TransformationEstimationPointToPoint(False), given the sample list
+    (ransac_samples(C, ransac_n, max_iteration, seed) unless passed): rounds
+    of round_size iterations — host Umeyama and checkers, one sweep for the
+    exact inlier counts of the survivors, the sequential rule replayed on the
+    host.  The result does not depend on round_size.  Returns the winning
+    transformation, its iteration index (-1: none scored better than nothing),
+    the number of iterations processed, the correspondence fitness and rmse."""
+    s, t, c = _corr_inputs(src, tgt, corres)
+    C = c.shape[0]
+    if ransac_n < 3 or C < ransac_n or max_correspondence_distance <= 0.0:
+        return {"transformation": np.eye(4), "best_iteration": -1, "processed": 0, "scored": 0, "corr_fitness": 0.0,
+                "corr_rmse": 0.0}
+    max_iteration = max(int(max_iteration), 0)
+    if samples is None:
+        samples = ransac_samples(C, ransac_n, max_iteration, seed)
+    ch = c.cpu().numpy()
+    ps = s.cpu().numpy().astype(np.float64)[ch[:, 0]]
+    qt = t.cpu().numpy().astype(np.float64)[ch[:, 1]]
+    return corr_ransac_rounds(
+        ps, qt, samples, ransac_n, edge_similarity, distance_threshold, max_iteration, confidence, round_size,
+        lambda T: corr_count(s, t, c, T, max_correspondence_distance),
+        lambda T: corr_error2(s, t, c, T, max_correspondence_distance))
+
+
+def corr_ransac_rounds(ps: np.ndarray, qt: np.ndarray, samples, ransac_n: int, edge_similarity: float,
+                       distance_threshold: float, max_iteration: int, confidence: float, round_size: int,
+                       count_fn, err2_fn):
+    """The host side of registration_ransac_based_on_correspondence: ps, qt (C,
+    3) float64 are the correspondences' source and target points; count_fn /
+    err2_fn score a batch of transformations (H, 4, 4) -> (H,) (the GPU sweeps
+    corr_count and corr_error2)."""
+    C = len(ps)
+    smp = _c(samples, np.int32).reshape(-1, ransac_n)[:max_iteration]
+    max_iteration = smp.shape[0]
+    rp = CorrRansacReplay(C, ransac_n, max_iteration, confidence)
+    round_size = max(int(round_size), 1)
+    scored = 0
+    for r0 in range(0, max_iteration, round_size):
+        if rp.stopped(r0):
+            break
+        sm = smp[r0:min(r0 + round_size, max_iteration)]
+        coords = np.stack([ps[sm], qt[sm]], axis=2)  # (H, ransac_n, 2, 3)
+        T = umeyama_from_samples(coords)
+        surv = np.nonzero(corr_check(coords, T, edge_similarity, distance_threshold))[0]
+        # hypotheses past est_k are never scored: est_k only falls
+        surv = surv[r0 + surv < rp.est_k]
+        if len(surv) == 0:
+            continue
+        itrs = r0 + surv
+        Ts = T[surv]
+        counts = count_fn(Ts)
+        need, need_best = rp.consults(itrs, counts)
+        Tq = [Ts[p] for p in need] + ([rp.best_T] if need_best and rp.best_err2 is None else [])
+        err = {}
+        if Tq:
+            e2 = err2_fn(np.stack(Tq))
+            err = {p: float(e2[k]) for k, p in enumerate(need)}
+            if len(Tq) > len(need):
+                rp.best_err2 = float(e2[len(need)])
+        for p, itr in enumerate(itrs):
+            if not rp.feed(int(itr), counts[p], Ts[p], err.get(p)):
+                break
+            scored += 1
+    res = {"transformation": rp.best_T, "best_iteration": rp.best_itr, "processed": rp.processed(), "scored": scored,
+           "corr_fitness": 0.0, "corr_rmse": 0.0}
+    if rp.best_count > 0:
+        if rp.best_err2 is None:
+            rp.best_err2 = float(err2_fn(rp.best_T[None])[0])
+        res["corr_fitness"] = rp.best_count / C
+        res["corr_rmse"] = float(np.sqrt(rp.best_err2 / rp.best_count))
+    return res
+
+
 _absmax = absmax  # for ICPTarget.accumulate, whose parameter of that name shadows it

@@ -69,6 +69,90 @@ def resolve_estimation(estimation, with_scaling: bool = False):
                      "TransformationEstimationPointToPoint / TransformationEstimationPointToPlane object")
 
 
+class RANSACConvergenceCriteria:
+    """Open3D's criteria of the RANSAC registrations (max_iteration, confidence)."""
+
+    def __init__(self, max_iteration: int = 100000, confidence: float = 0.999):
+        self.max_iteration = int(max_iteration)
+        self.confidence = float(confidence)
+
+    def __repr__(self):
+        return f"RANSACConvergenceCriteria(max_iteration={self.max_iteration}, confidence={self.confidence})"
+
+
+class CorrespondenceCheckerBasedOnEdgeLength:
+    def __init__(self, similarity_threshold: float = 0.9):
+        self.similarity_threshold = float(similarity_threshold)
+
+    def __repr__(self):
+        return f"CorrespondenceCheckerBasedOnEdgeLength(similarity_threshold={self.similarity_threshold})"
+
+
+class CorrespondenceCheckerBasedOnDistance:
+    def __init__(self, distance_threshold: float):
+        self.distance_threshold = float(distance_threshold)
+
+    def __repr__(self):
+        return f"CorrespondenceCheckerBasedOnDistance(distance_threshold={self.distance_threshold})"
+
+
+def resolve_checkers(checkers):
+    """-> (edge similarity, distance threshold) of a list of correspondence
+    checkers, -1.0 where there is none (duck-typed on similarity_threshold /
+    distance_threshold, so genuine Open3D objects work too; several of a kind:
+    the strictest).  ValueError for CorrespondenceCheckerBasedOnNormal or
+    anything else."""
+    edge, dist = -1.0, -1.0
+    for c in checkers or []:
+        if hasattr(c, "normal_angle_threshold"):
+            raise ValueError("CorrespondenceCheckerBasedOnNormal is not supported")
+        if hasattr(c, "similarity_threshold"):
+            edge = max(edge, float(c.similarity_threshold))
+        elif hasattr(c, "distance_threshold"):
+            d = float(c.distance_threshold)
+            dist = d if dist < 0.0 else min(dist, d)
+        else:
+            raise ValueError(f"unsupported correspondence checker {c!r}")
+    return edge, dist
+
+
+class Feature:
+    """Mirror of o3d.pipelines.registration.Feature: .data is the (dim, N)
+    float64 array (Open3D's layout); the (N, dim) float32 device tensor the
+    kernels produced stays in ._dev for the matcher."""
+
+    def __init__(self, dev=None, data=None):
+        self._dev = dev
+        self._data = None if data is None else data
+
+    @property
+    def data(self):
+        if self._data is None:
+            import numpy as np
+
+            self._data = np.ascontiguousarray(self._dev.detach().cpu().numpy().astype(np.float64).T)
+        return self._data
+
+    def device_rows(self):
+        """(N, dim) float32 on the device."""
+        if self._dev is None:
+            import numpy as np
+            import torch
+
+            self._dev = torch.as_tensor(np.ascontiguousarray(np.asarray(self._data, np.float32).T),
+                                        device=N.default_device())
+        return self._dev
+
+    def dimension(self) -> int:
+        return int(self._dev.shape[1] if self._dev is not None else self._data.shape[0])
+
+    def num(self) -> int:
+        return int(self._dev.shape[0] if self._dev is not None else self._data.shape[1])
+
+    def __repr__(self):
+        return f"Feature class with dimension = {self.dimension()} and num = {self.num()}"
+
+
 def resolve(param):
     """-> (mode, knn, radius) for the C-ABI."""
     if param is None:
