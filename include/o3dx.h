@@ -1161,6 +1161,58 @@ int o3dx_corr_error2(const float* src_dev, const float* tgt_dev, const int32_t* 
                      const double* T_host, int num_hypotheses, double max_distance, double* sums_host,
                      int64_t* counts_host, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- uncapped radius sweeps: neighbour count, ISS keypoints (additive to ABI 7)
+ * One neighbourhood rule: j is in N_r(i) when d^2(i,j) < r * r (strict; i
+ * itself is in), d^2 in float64 as ((dx dx) + dy dy) + dz dz on the float64
+ * values of the coordinates (the rule of the radius normals).  The *_f64
+ * entries decide every pair, and take every moment, from the caller's float64
+ * coordinates.  radius finite and > 0, 1 <= n < 2^31, else EINVAL; ENOMEM for a
+ * workspace below the entry's own *_workspace_bytes(n).  Outputs are
+ * bit-identical run to run (no float atomics).
+ *
+ * o3dx_radius_count: count_dev[i] = min(|N_r(i)|, cap) (cap <= 0: no cap; the
+ *   sweep of a point stops at cap).  Replaces the per-point SearchRadius of
+ *   Open3D's PointCloud::RemoveRadiusOutliers (keep when the count > nb_points).
+ * o3dx_iss_saliency: count_dev[i] = |N_r(i)| and s_dev[i], the ISS saliency of
+ *   o3d.geometry.keypoint.compute_iss_keypoints (ComputeKeypointsISS' first
+ *   loop): 0 when the count < min_neighbors or when every |entry| of the
+ *   neighbours' covariance C (sum p p^T / k - mu mu^T, float64) is <= 1e-12;
+ *   else with C's eigenvalues e1 >= e2 >= e3 (Eberly's non-iterative solve),
+ *   s = e3 when e2 / e1 < gamma_21 and e3 / e2 < gamma_32 (NaN ratios compare
+ *   false), else 0.  s is a function of the neighbour SET alone: the moments
+ *   are taken about the set's first member in cell-sorted order and added in
+ *   ascending cell-sorted position per query, so two points with the same
+ *   neighbours get the same bits (Open3D adds them in kd-tree result order).
+ * o3dx_iss_nms: ComputeKeypointsISS' second loop.  i is a keypoint when
+ *   s[i] > 0, |N_r(i)| >= min_neighbors and no j in N_r(i) has s[i] < s[j]
+ *   (strict: exact ties both survive).  idx_out_dev (capacity n) receives the
+ *   keypoints in ascending index order (Open3D's order is arbitrary),
+ *   *count_host their number.
+ * o3dx_nn_distance_sum: *sum_host = the sum of sqrt(d2_dev[i * k + col]) over
+ *   the rows with cnt_dev[i] > col, float64 in a fixed order (ComputeModel-
+ *   Resolution's sum over a 2-NN search: k = 2, col = 1).  ws: >= 256 bytes. */
+size_t o3dx_radius_count_workspace_bytes(int64_t n);
+int o3dx_radius_count(const float* xyz_dev, int64_t n, double radius, int cap, int32_t* count_dev, void* ws,
+                      size_t ws_bytes, void* stream);
+size_t o3dx_radius_count_f64_workspace_bytes(int64_t n);
+int o3dx_radius_count_f64(const double* xyz_dev, int64_t n, double radius, int cap, int32_t* count_dev, void* ws,
+                          size_t ws_bytes, void* stream);
+size_t o3dx_iss_saliency_workspace_bytes(int64_t n);
+int o3dx_iss_saliency(const float* xyz_dev, int64_t n, double radius, double gamma_21, double gamma_32,
+                      int min_neighbors, double* s_dev, int32_t* count_dev, void* ws, size_t ws_bytes, void* stream);
+size_t o3dx_iss_saliency_f64_workspace_bytes(int64_t n);
+int o3dx_iss_saliency_f64(const double* xyz_dev, int64_t n, double radius, double gamma_21, double gamma_32,
+                          int min_neighbors, double* s_dev, int32_t* count_dev, void* ws, size_t ws_bytes,
+                          void* stream);
+size_t o3dx_iss_nms_workspace_bytes(int64_t n);
+int o3dx_iss_nms(const float* xyz_dev, int64_t n, const double* s_dev, double radius, int min_neighbors,
+                 int32_t* idx_out_dev, int64_t* count_host, void* ws, size_t ws_bytes, void* stream);
+size_t o3dx_iss_nms_f64_workspace_bytes(int64_t n);
+int o3dx_iss_nms_f64(const double* xyz_dev, int64_t n, const double* s_dev, double radius, int min_neighbors,
+                     int32_t* idx_out_dev, int64_t* count_host, void* ws, size_t ws_bytes, void* stream);
+int o3dx_nn_distance_sum(const double* d2_dev, const int32_t* cnt_dev, int64_t n, int k, int col, double* sum_host,
+                         void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

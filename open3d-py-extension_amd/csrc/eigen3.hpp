@@ -361,4 +361,47 @@ O3DX_HD inline void fast_eigen3x3(const double c[6], double out[3]) {
   }
 }
 
+// ------------------------------------------------------------ all three eigenvalues
+// Eberly's non-iterative solve as above, the three eigenvalues instead of the
+// smallest eigenvector: ev[0] <= ev[1] <= ev[2] (beta0 <= beta1 <= beta2 by
+// construction).  Scaled by the largest |entry|, so a matrix whose diagonal
+// rounded below zero keeps its order.  Error: a few ulps of the largest
+// |entry| on each value (the ISS saliency, keypoint.hip).
+O3DX_HD inline void eigen3_values(const double c[6], double ev[3]) {
+  double mc = fabs(c[0]);
+  for (int j = 1; j < 6; ++j) mc = fmax(mc, fabs(c[j]));
+  if (!(mc > 0)) {  // the zero matrix (or NaN entries)
+    ev[0] = ev[1] = ev[2] = mc;
+    return;
+  }
+  const double a00 = c[0] / mc, a01 = c[1] / mc, a02 = c[2] / mc, a11 = c[3] / mc, a12 = c[4] / mc, a22 = c[5] / mc;
+  const double norm = a01 * a01 + a02 * a02 + a12 * a12;
+  double e0, e1, e2;
+  if (norm > 0) {
+    const double q = (a00 + a11 + a22) / 3;
+    const double b00 = a00 - q, b11 = a11 - q, b22 = a22 - q;
+    const double p = sqrt((b00 * b00 + b11 * b11 + b22 * b22 + norm * 2) / 6);
+    const double c00 = b11 * b22 - a12 * a12;
+    const double c01 = a01 * b22 - a12 * a02;
+    const double c02 = a01 * a12 - b11 * a02;
+    const double det = (b00 * c00 - a01 * c01 + a02 * c02) / (p * p * p);
+    const double half_det = fmin(fmax(det * 0.5, -1.0), 1.0);
+    const double angle = acos(half_det) / (double)3;
+    const double two_thirds_pi = 2.09439510239319549;
+    const double beta2 = cos(angle) * 2;
+    const double beta0 = cos(angle + two_thirds_pi) * 2;
+    const double beta1 = -(beta0 + beta2);
+    e0 = q + p * beta0;
+    e1 = q + p * beta1;
+    e2 = q + p * beta2;
+  } else {  // diagonal: its entries, sorted
+    e0 = fmin(a00, fmin(a11, a22));
+    e1 = fmax(fmin(a00, a11), fmin(fmax(a00, a11), a22));
+    e2 = fmax(a00, fmax(a11, a22));
+  }
+  ev[0] = e0 * mc;
+  ev[1] = e1 * mc;
+  ev[2] = e2 * mc;
+}
+
 }  // namespace o3dx

@@ -852,6 +852,59 @@ class PointCloudUtility(PointCloudSelections):
         kept = keep.cpu().numpy().tolist()
         return self._select_by_idx(keep), kept
 
+    def _require_finite_points(self, what: str):
+        """ValueError when a coordinate is NaN or infinite (checked where the
+        points live; a host cloud needs no GPU for it)."""
+        src = self._pts_host if self._pts_host is not None else self._pts
+        if src is None:
+            return
+        ok = bool(np.isfinite(src).all()) if isinstance(src, np.ndarray) else bool(torch.isfinite(src).all().item())
+        if not ok:
+            raise ValueError(f"{what}: the cloud has non-finite coordinates")
+
+    def remove_radius_outlier(self, nb_points: int, radius: float, print_progress: bool = False):
+        """Open3D RemoveRadiusOutliers: keep the points with more than
+        nb_points points within radius (d^2 < radius^2, the point itself
+        counted; ops.radius_count, the sweep stops at nb_points + 1).
+        Returns (cloud, kept index list), as remove_statistical_outlier."""
+        radius = float(radius)
+        if int(nb_points) < 1 or not np.isfinite(radius) or radius < 0.0:
+            raise ValueError("Illegal input parameters, the number of points must be positive and the radius "
+                             "finite and not negative.")
+        self._require_finite_points("remove_radius_outlier")
+        if not self.has_points():
+            return self.__class__(), []
+        cnt = ops.radius_count(self._hot_points(), radius, cap=int(nb_points) + 1)
+        keep = torch.nonzero(cnt > int(nb_points)).reshape(-1)
+        return self._select_by_idx(keep), keep.cpu().numpy().tolist()
+
+    def get_index_by_iss_keypoints(self, salient_radius: float = 0.0, non_max_radius: float = 0.0,
+                                   gamma_21: float = 0.975, gamma_32: float = 0.975, min_neighbors: int = 5):
+        """The ISS keypoints (o3d.geometry.keypoint.compute_iss_keypoints) as
+        ascending int64 numpy indices (ops.iss_keypoints; Open3D's order is
+        arbitrary).  Radii of 0.0: 6 and 4 model resolutions."""
+        for name, v in (("salient_radius", salient_radius), ("non_max_radius", non_max_radius)):
+            if not np.isfinite(float(v)) or float(v) < 0.0:
+                raise ValueError(f"{name} must be finite and >= 0, got {v}")
+        for name, v in (("gamma_21", gamma_21), ("gamma_32", gamma_32)):
+            if not np.isfinite(float(v)):
+                raise ValueError(f"{name} must be finite, got {v}")
+        self._require_finite_points("compute_iss_keypoints")
+        if not self.has_points():
+            return np.zeros(0, np.int64)
+        idx, _, _ = ops.iss_keypoints(self._hot_points(), float(salient_radius), float(non_max_radius),
+                                      float(gamma_21), float(gamma_32), int(min_neighbors))
+        return idx.cpu().numpy().astype(np.int64)
+
+    def compute_iss_keypoints(self, salient_radius: float = 0.0, non_max_radius: float = 0.0,
+                              gamma_21: float = 0.975, gamma_32: float = 0.975, min_neighbors: int = 5):
+        """A new cloud of the ISS keypoints, every attribute following
+        (get_index_by_iss_keypoints, _select_by_idx)."""
+        idx = self.get_index_by_iss_keypoints(salient_radius, non_max_radius, gamma_21, gamma_32, min_neighbors)
+        if not self.has_points():
+            return self.__class__()
+        return self._select_by_idx(idx)
+
     def merge_pcds(self, raw_pcds, rgb: bool = False, intensity: bool = False, normals: bool = False,
                    labels: bool = False):
         pcds = [p if isinstance(p, PointCloudBase) else self.__class__(p) for p in raw_pcds]

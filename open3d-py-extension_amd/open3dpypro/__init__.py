@@ -15,5 +15,7 @@ from .PointCloud import (KDTreeGrid, PointCloud, PointCloudAdvanceIO, PointCloud
 from .PointCloudMat import *  # noqa: F401,F403
 from .processors import PointCloudMatProcessors, Processors  # noqa: F401
 from . import processors  # noqa: F401
+from . import keypoint  # noqa: F401
+from .keypoint import compute_iss_keypoints  # noqa: F401
 
 __version__ = "0.1.0"

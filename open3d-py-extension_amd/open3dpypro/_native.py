@@ -191,6 +191,20 @@ _SIGS = {
     "o3dx_corr_count_workspace_bytes": (_SZ, [_I64, _I32]),
     "o3dx_corr_count": (_I32, [_P, _P, _P, _I64, _P, _I32, _D, _P, _P, _SZ, _P]),
     "o3dx_corr_error2": (_I32, [_P, _P, _P, _I64, _P, _I32, _D, _P, _P, _P, _SZ, _P]),
+    # uncapped radius sweeps: neighbour count, ISS keypoints (additive to ABI 7)
+    "o3dx_radius_count_workspace_bytes": (_SZ, [_I64]),
+    "o3dx_radius_count": (_I32, [_P, _I64, _D, _I32, _P, _P, _SZ, _P]),
+    "o3dx_radius_count_f64_workspace_bytes": (_SZ, [_I64]),
+    "o3dx_radius_count_f64": (_I32, [_P, _I64, _D, _I32, _P, _P, _SZ, _P]),
+    "o3dx_iss_saliency_workspace_bytes": (_SZ, [_I64]),
+    "o3dx_iss_saliency": (_I32, [_P, _I64, _D, _D, _D, _I32, _P, _P, _P, _SZ, _P]),
+    "o3dx_iss_saliency_f64_workspace_bytes": (_SZ, [_I64]),
+    "o3dx_iss_saliency_f64": (_I32, [_P, _I64, _D, _D, _D, _I32, _P, _P, _P, _SZ, _P]),
+    "o3dx_iss_nms_workspace_bytes": (_SZ, [_I64]),
+    "o3dx_iss_nms": (_I32, [_P, _I64, _P, _D, _I32, _P, _P, _P, _SZ, _P]),
+    "o3dx_iss_nms_f64_workspace_bytes": (_SZ, [_I64]),
+    "o3dx_iss_nms_f64": (_I32, [_P, _I64, _P, _D, _I32, _P, _P, _P, _SZ, _P]),
+    "o3dx_nn_distance_sum": (_I32, [_P, _P, _I64, _I32, _I32, _P, _P, _SZ, _P]),
 }
 
 _lib = None

@@ -1601,3 +1601,121 @@ def corr_ransac_rounds(ps: np.ndarray, qt: np.ndarray, samples, ransac_n: int, e
 
 
 _absmax = absmax  # for ICPTarget.accumulate, whose parameter of that name shadows it
+
+
+# ---------------------------------------------------------------- radius sweeps, ISS keypoints
+def _sweep_points(xyz):
+    f64 = _is64(xyz)
+    return (_xyz64(xyz) if f64 else _xyz(xyz)), f64
+
+
+def _check_radius(radius, what="radius"):
+    radius = float(radius)
+    if not np.isfinite(radius) or radius < 0.0:
+        raise ValueError(f"{what} must be finite and >= 0, got {radius}")
+    return radius
+
+
+def radius_count(xyz: torch.Tensor, radius: float, cap=None) -> torch.Tensor:
+    """|N_r(i)| per point (o3dx_radius_count): the number of points with
+    d^2 < radius^2 (strict, the point itself included, float64 d^2), an (n,)
+    int32 device tensor; with cap, min(count, cap) (the sweep stops there).
+    float64 points: o3dx_radius_count_f64."""
+    radius = _check_radius(radius)
+    x, f64 = _sweep_points(xyz)
+    n = x.shape[0]
+    dev = x.device
+    count = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n == 0 or radius == 0.0:  # d^2 < 0 holds for no pair
+        return count
+    L = N.load()
+    wsb, fn = ((L.o3dx_radius_count_f64_workspace_bytes, L.o3dx_radius_count_f64) if f64 else
+               (L.o3dx_radius_count_workspace_bytes, L.o3dx_radius_count))
+    ws = N.workspace(wsb(n), dev)
+    N.check(fn(N.ptr(x), n, radius, 0 if cap is None else max(int(cap), 1), N.ptr(count), N.ptr(ws), ws.numel(),
+               N.stream_ptr(dev)), "radius_count")
+    return count
+
+
+def model_resolution(xyz: torch.Tensor) -> float:
+    """Open3D's ComputeModelResolution: (the sum over the points of sqrt(d^2)
+    to entry [1] of their 2-NN list, where there is one) / n.  The search is
+    ops.knn_search; the float64 sum runs on the device in a fixed order
+    (o3dx_nn_distance_sum), so the value is the same bits run to run."""
+    x, _ = _sweep_points(xyz)
+    n = x.shape[0]
+    if n == 0:
+        return 0.0
+    _, d2, cnt = knn_search(x, x, mode=N.SEARCH_KNN, knn=2)
+    d2 = d2.contiguous()
+    cnt = cnt.contiguous()
+    L = N.load()
+    out = np.zeros(1, np.float64)
+    ws = N.workspace(256, x.device)
+    N.check(L.o3dx_nn_distance_sum(N.ptr(d2), N.ptr(cnt), n, int(d2.shape[1]), 1, _np_ptr(out), N.ptr(ws),
+                                   ws.numel(), N.stream_ptr(x.device)), "model_resolution")
+    return float(out[0]) / n
+
+
+def iss_saliency(xyz: torch.Tensor, radius: float, gamma_21: float = 0.975, gamma_32: float = 0.975,
+                 min_neighbors: int = 5):
+    """(s (n,) float64, count (n,) int32) on the device: the ISS saliency and
+    |N_radius(i)| of every point (o3dx_iss_saliency; include/o3dx.h states the
+    rule).  float64 points: o3dx_iss_saliency_f64."""
+    radius = _check_radius(radius)
+    x, f64 = _sweep_points(xyz)
+    n = x.shape[0]
+    dev = x.device
+    s = torch.zeros(n, dtype=torch.float64, device=dev)
+    count = torch.zeros(n, dtype=torch.int32, device=dev)
+    if n == 0 or radius == 0.0:
+        return s, count
+    L = N.load()
+    wsb, fn = ((L.o3dx_iss_saliency_f64_workspace_bytes, L.o3dx_iss_saliency_f64) if f64 else
+               (L.o3dx_iss_saliency_workspace_bytes, L.o3dx_iss_saliency))
+    ws = N.workspace(wsb(n), dev)
+    N.check(fn(N.ptr(x), n, radius, float(gamma_21), float(gamma_32), int(min_neighbors), N.ptr(s), N.ptr(count),
+               N.ptr(ws), ws.numel(), N.stream_ptr(dev)), "iss_saliency")
+    return s, count
+
+
+def iss_nms(xyz: torch.Tensor, s: torch.Tensor, radius: float, min_neighbors: int = 5) -> torch.Tensor:
+    """The ISS keypoints of a saliency (o3dx_iss_nms): ascending int32 device
+    indices of the points with s > 0, at least min_neighbors points within
+    radius and no neighbour of larger s.  float64 points: o3dx_iss_nms_f64."""
+    radius = _check_radius(radius)
+    x, f64 = _sweep_points(xyz)
+    n = x.shape[0]
+    dev = x.device
+    if n == 0 or radius == 0.0:
+        return torch.zeros(0, dtype=torch.int32, device=dev)
+    N.require_device(s, "s")
+    sv = s.to(torch.float64).contiguous()
+    if sv.shape != (n,):
+        raise RuntimeError(f"s must have shape ({n},), got {tuple(sv.shape)}")
+    L = N.load()
+    wsb, fn = ((L.o3dx_iss_nms_f64_workspace_bytes, L.o3dx_iss_nms_f64) if f64 else
+               (L.o3dx_iss_nms_workspace_bytes, L.o3dx_iss_nms))
+    ws = N.workspace(wsb(n), dev)
+    idx = torch.empty(n, dtype=torch.int32, device=dev)
+    cnt = np.zeros(1, np.int64)
+    N.check(fn(N.ptr(x), n, N.ptr(sv), radius, int(min_neighbors), N.ptr(idx), _np_ptr(cnt), N.ptr(ws), ws.numel(),
+               N.stream_ptr(dev)), "iss_nms")
+    return idx[:int(cnt[0])]
+
+
+def iss_keypoints(xyz: torch.Tensor, salient_radius: float = 0.0, non_max_radius: float = 0.0,
+                  gamma_21: float = 0.975, gamma_32: float = 0.975, min_neighbors: int = 5):
+    """o3d.geometry.keypoint.compute_iss_keypoints on the device: (idx,
+    salient_radius, non_max_radius), idx the keypoints as ascending int32
+    device indices and the radii as used (6 and 4 model resolutions when
+    either is 0.0)."""
+    salient_radius = _check_radius(salient_radius, "salient_radius")
+    non_max_radius = _check_radius(non_max_radius, "non_max_radius")
+    x, _ = _sweep_points(xyz)
+    if salient_radius == 0.0 or non_max_radius == 0.0:
+        res = model_resolution(x)
+        salient_radius, non_max_radius = 6.0 * res, 4.0 * res
+    s, _ = iss_saliency(x, salient_radius, gamma_21, gamma_32, min_neighbors)
+    idx = iss_nms(x, s, non_max_radius, min_neighbors)
+    return idx, salient_radius, non_max_radius

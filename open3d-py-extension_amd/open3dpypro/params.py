@@ -149,6 +149,30 @@ class Feature:
     def num(self) -> int:
         return int(self._dev.shape[0] if self._dev is not None else self._data.shape[1])
 
+    def select_by_index(self, indices, invert: bool = False):
+        """Open3D >= 0.18's Feature.select_by_index: a new Feature of the
+        listed columns (invert: of every other column), in ascending column
+        order.  On the device rows when they exist, else on .data (no GPU)."""
+        import numpy as np
+
+        if hasattr(indices, "detach"):
+            indices = indices.detach().cpu().numpy()
+        idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+        n = self.num()
+        if idx.size and (idx.min() < 0 or idx.max() >= n):
+            raise IndexError(f"feature index outside [0, {n})")
+        mask = np.zeros(n, dtype=bool)
+        mask[idx] = True
+        if invert:
+            mask = ~mask
+        sel = np.nonzero(mask)[0]
+        if self._dev is not None:
+            import torch
+
+            rows = self._dev.index_select(0, torch.as_tensor(sel, device=self._dev.device)).contiguous()
+            return Feature(dev=rows)
+        return Feature(data=np.ascontiguousarray(np.asarray(self._data)[:, sel]))
+
     def __repr__(self):
         return f"Feature class with dimension = {self.dimension()} and num = {self.num()}"
 
