@@ -451,6 +451,13 @@ int o3dx_ransac_tied(const int64_t* counts_host, const double* planes_host,
 int o3dx_ransac_select(const int64_t* counts_host, const double* sums_host,
                        const double* planes_host, int num_hypotheses,
                        int64_t n, int ransac_n, double probability);
+/* The early-stop point the three replays above set at a new best fitness:
+ * 0 for fitness >= 1; num_hypotheses (no early stop) when the quotient
+ * log(1 - probability) / log(1 - fitness^ransac_n) is not >= 0 (-inf or NaN
+ * once fitness^ransac_n < 2^-53); else the quotient, capped at
+ * num_hypotheses, truncated.  Host-only. */
+int64_t o3dx_ransac_break_iteration(double fitness, int ransac_n, double probability,
+                                    int num_hypotheses);
 int o3dx_plane_inliers(const float* xyz_dev, int64_t n, const double* plane_host,
                        double distance_threshold, int32_t* idx_out_dev,
                        int64_t* count_host, void* ws, size_t ws_bytes,

@@ -1595,6 +1595,18 @@ static int run_abs_sum(const T* xyz, int64_t n, const double* planes, const int3
   return 0;
 }
 
+// Open3D's early-stop point for a new best fitness: log(1 - p) / log(1 - fit^ransac_n),
+// capped at H.  Once fit^ransac_n drops below 2^-53 the denominator is log(1) = +0 and the
+// quotient -inf (NaN for a p that small too), whose conversion to size_t is
+// undefined; the true quotient is huge and positive, so that means no early
+// stop: H, which the iteration counter never passes.
+static size_t ransac_break_iteration(double fit, int ransac_n, double probability, int H) {
+  if (fit >= 1.0) return 0;
+  const double q = std::log(1 - probability) / std::log(1 - std::pow(fit, ransac_n));
+  if (!(q >= 0)) return (size_t)H;
+  return (size_t)std::min(q, (double)H);
+}
+
 static int select_best(const int64_t* counts, const double* sums, const double* planes, int H, int64_t n, int ransac_n,
                        double probability) {
   double best_fit = 0, best_rmse = 0;
@@ -1610,12 +1622,7 @@ static int select_best(const int64_t* counts, const double* sums, const double* 
       best_fit = fit;
       best_rmse = rmse;
       best = it;
-      if (best_fit < 1.0) {
-        double bi = std::min(std::log(1 - probability) / std::log(1 - std::pow(best_fit, ransac_n)), (double)H);
-        break_iteration = (size_t)bi;
-      } else {
-        break_iteration = 0;
-      }
+      break_iteration = ransac_break_iteration(best_fit, ransac_n, probability, H);
     }
     iteration_count++;
   }
@@ -1647,13 +1654,7 @@ static std::vector<int32_t> tied_hypotheses(const std::vector<int64_t>& counts, 
       if (counts[it] > best) {
         flush();
         best = counts[it];
-        const double fit = (double)best / (double)n;
-        if (fit < 1.0) {
-          double bi = std::min(std::log(1 - probability) / std::log(1 - std::pow(fit, ransac_n)), (double)H);
-          break_iteration = (size_t)bi;
-        } else {
-          break_iteration = 0;
-        }
+        break_iteration = ransac_break_iteration((double)best / (double)n, ransac_n, probability, H);
       }
       run.push_back(it);
     }
@@ -1686,13 +1687,7 @@ static std::vector<int32_t> needed_exact(const int64_t* v, const uint8_t* known,
       if (!known[it]) out.push_back(it);
       if (v[it] > best) {
         best = v[it];
-        const double fit = (double)best / (double)n;
-        if (fit < 1.0) {
-          double bi = std::min(std::log(1 - probability) / std::log(1 - std::pow(fit, ransac_n)), (double)H);
-          break_iteration = (size_t)bi;
-        } else {
-          break_iteration = 0;
-        }
+        break_iteration = ransac_break_iteration((double)best / (double)n, ransac_n, probability, H);
       }
     }
     iteration_count++;
@@ -1937,6 +1932,10 @@ extern "C" int o3dx_ransac_tied(const int64_t* counts, const double* planes, int
   std::memcpy(out, t.data(), t.size() * sizeof(int32_t));
   *n_out = (int32_t)t.size();
   return 0;
+}
+
+extern "C" int64_t o3dx_ransac_break_iteration(double fitness, int ransac_n, double probability, int num_hypotheses) {
+  return (int64_t)ransac_break_iteration(fitness, ransac_n, probability, std::max(num_hypotheses, 0));
 }
 
 extern "C" int o3dx_ransac_select(const int64_t* counts, const double* sums, const double* planes, int H, int64_t n,
@@ -2371,6 +2370,32 @@ extern "C" int o3dx_segment_plane_f64(const double* xyz, int64_t n, double thr, 
     O3DX_TRY(reduce_columns_i64(w.mom_part2, nb2, 12, w.fin + 8, s));
     O3DX_HIP(hipGetLastError());
     O3DX_TRY(read_back(fin, w.fin, sizeof(fin), s));
+    // The cloud's extent bounds the centred products, but inliers that span
+    // far less (one site of a collapsed scan: micrometres in a kilometre)
+    // leave their sums a few quanta, or none: the zero plane.  While the
+    // largest diagonal sum holds fewer than 2^30 quanta the pass runs again
+    // with the quantum from the sums themselves: a diagonal term is at most
+    // its sum, an off-diagonal one at most the larger of its two diagonal
+    // terms, and each sum absorbed at most k roundings of half a quantum.
+    for (int round = 0; round < 4 && fin[0] > 0; ++round) {
+      int64_t fxd[24];
+      double d2[6];
+      fx_pack(fin + 8, q2, 6, fxd);
+      fx_to_double(fxd, 6, d2);
+      const double D = std::max(d2[0], std::max(d2[3], d2[5]));
+      if (!(D < std::ldexp(1.0, q2[0] + 30))) break;
+      const int qn = fx_exp((D + (double)fin[0] * std::ldexp(1.0, q2[0])) * 1.03);
+      if (qn >= q2[0]) break;
+      for (int a = 0; a < 6; ++a) {
+        q2[a] = qn;
+        sc2.s[a] = fx_scale(qn);
+      }
+      hipLaunchKernelGGL(k_plane_moments_c<double>, dim3(nb2), dim3(kBlock), 0, s, xyz, inliers_out, w.fin, w.fin + 2,
+                         q1[0], q1[1], q1[2], sc2, w.mom_part2);
+      O3DX_TRY(reduce_columns_i64(w.mom_part2, nb2, 12, w.fin + 8, s));
+      O3DX_HIP(hipGetLastError());
+      O3DX_TRY(read_back(fin, w.fin, sizeof(fin), s));
+    }
   }
   const int64_t k = fin[0];
   *n_inliers_host = k;

@@ -1423,6 +1423,10 @@ class PointCloud(PointCloudAdvanceIO):
             except RuntimeError as e:
                 print(e)
                 break
+            if inl.numel() == 0:
+                # every hypothesis degenerate (a collinear or coincident
+                # remainder): the zero plane, and `rest` cannot change
+                break
             planes.append(plane)
             inliers = rest._select_by_idx(inl)
             pcds.append(inliers)

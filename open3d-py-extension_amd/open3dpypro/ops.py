@@ -895,6 +895,13 @@ def ransac_select(counts, sums, planes, n, ransac_n, probability=0.99999999) -> 
                                            float(probability)))
 
 
+def ransac_break_iteration(fitness: float, ransac_n: int, probability: float, num_iterations: int) -> int:
+    """The selection replays' early-stop point for a new best fitness
+    (o3dx_ransac_break_iteration): num_iterations where the quotient underflows."""
+    return int(N.load().o3dx_ransac_break_iteration(float(fitness), int(ransac_n), float(probability),
+                                                    int(num_iterations)))
+
+
 def plane_inliers(xyz: torch.Tensor, plane, distance_threshold: float) -> torch.Tensor:
     x = _xyz(xyz)
     L = N.load()

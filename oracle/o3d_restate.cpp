@@ -883,6 +883,18 @@ void oref_ransac_samples(int64_t n, int ransac_n, int iters, uint64_t seed, int3
   }
 }
 
+// [upstream] SegmentPlane's early-stop point, log(1 - p) / log(1 - fit^ransac_n)
+// capped at the iteration count.  Upstream converts the quotient to size_t as
+// it is; for fit^ransac_n < 2^-53 it is -inf (or NaN), the conversion is
+// undefined and x86-64 happens to give 2^63: no early stop.  That meaning is
+// stated here instead of left to the conversion.
+size_t ransac_break_iteration(double fit, int ransac_n, double prob, int iters) {
+  if (fit >= 1.0) return 0;
+  const double q = std::log(1 - prob) / std::log(1 - std::pow(fit, ransac_n));
+  if (!(q >= 0)) return (size_t)iters;
+  return (size_t)std::min(q, (double)iters);
+}
+
 // Reference: segment_plane (PointCloud.py:75-77).  [upstream]
 // PointCloud::SegmentPlane + EvaluateRANSACBasedOnDistance + GetPlaneFromPoints,
 // with the iteration loop replayed sequentially (1 OpenMP thread semantics);
@@ -942,12 +954,7 @@ int oref_segment_plane(const double* xyz, int64_t n, double thr, int ransac_n, i
       best_fit = fit;
       best_rmse = rmse;
       best = it;
-      if (best_fit < 1.0) {
-        double bi = std::min(std::log(1 - prob) / std::log(1 - std::pow(best_fit, ransac_n)), (double)iters);
-        break_iteration = (size_t)bi;
-      } else {
-        break_iteration = 0;
-      }
+      break_iteration = ransac_break_iteration(best_fit, ransac_n, prob, iters);
     }
     iteration_count++;
   }
@@ -972,6 +979,10 @@ int oref_segment_plane(const double* xyz, int64_t n, double thr, int ransac_n, i
   }
   plane_from_points(pts.data(), inliers, k, plane_out);
   return 0;
+}
+
+int64_t oref_ransac_break_iteration(double fit, int ransac_n, double prob, int iters) {
+  return (int64_t)ransac_break_iteration(fit, ransac_n, prob, iters);
 }
 
 void oref_plane_from_points(const double* xyz, const int64_t* idx, int64_t k, double* plane_out) {

@@ -54,6 +54,8 @@ def lib():
         L.oref_segment_plane.argtypes = [_P, _I64, _D, _I32, _I32, _D, _P, _P, _P, _P, _P, _P, _P]
         L.oref_segment_plane.restype = _I32
         L.oref_plane_from_points.argtypes = [_P, _P, _I64, _P]
+        L.oref_ransac_break_iteration.argtypes = [_D, _I32, _D, _I32]
+        L.oref_ransac_break_iteration.restype = _I64
         L.oref_registration_icp.argtypes = [_P, _I64, _P, _P, _I64, _D, _P, _I32, _D, _D,
                                             _P, _P, _P, _P, _P]
         L.oref_registration_icp.restype = _I32
@@ -213,6 +215,11 @@ def segment_plane(xyz, distance_threshold, ransac_n, num_iterations, samples,
     if rc != 0:
         raise RuntimeError("segment_plane: invalid arguments")
     return plane, inl[: int(ninl[0])].copy(), counts, sums, int(best[0])
+
+
+def ransac_break_iteration(fitness, ransac_n, probability, num_iterations):
+    """segment_plane's early-stop point for a new best fitness."""
+    return int(lib().oref_ransac_break_iteration(float(fitness), int(ransac_n), float(probability), int(num_iterations)))
 
 
 def plane_from_points(xyz, idx):

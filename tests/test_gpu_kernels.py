@@ -846,12 +846,9 @@ def test_mfma2_sweep_error_within_documented_bound(dev, monkeypatch):
     assert (ub >= (d < thr).sum(0)).all()
 
 
-def _open3d_counts(p64, planes, thr):
-    # Open3D's EvaluateRANSACBasedOnDistance predicate in its own order,
-    # |(a x + c z) + (b y + d)| < thr, elementwise float64 (no fma)
-    a, b, c, d = (planes[:, k][None, :] for k in range(4))
-    x, y, z = (p64[:, k][:, None] for k in range(3))
-    return (np.abs((a * x + c * z) + (b * y + d)) < thr).sum(0)
+# Open3D's EvaluateRANSACBasedOnDistance predicate in its own order,
+# |(a x + c z) + (b y + d)| < thr, elementwise float64 (no fma)
+from plane_edge_cases import open3d_counts as _open3d_counts  # noqa: E402
 
 
 @pytest.mark.parametrize("layout", ["straddle", "cube_plane"])
